@@ -2,6 +2,11 @@
 throughput in images/sec on N MI355X GPUs of one node.
 
   python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--model alexnet]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line; --dump-outputs DIR
+then also writes what a step of the timed path computes (see _dump_outputs).  Every further
+measurement of the same run sits behind --full.
 
 One process per GPU, RCCL over xGMI.  Under torchrun (WORLD_SIZE set) every rank runs
 the step; with --gpus N > 1 and no WORLD_SIZE this script launches
@@ -15,9 +20,9 @@ device: src/nnet/nnet_impl-inl.hpp:147-155, example/ImageNet/ImageNet.conf:108):
          global batch is 256*N: the per-GPU work of the conf's 1-GPU run, N times over;
   strong the global batch is --batch (256) and each rank takes ceil(256/N) rows, exactly
          the reference's multi-device semantics for the conf as written.
-With the default weak scaling and N > 1 the same run also times the strong configuration
-(ImageNet.conf's global batch of 256 over the N ranks) and reports it as the nested "strong"
-record of the one JSON line (--strong-record 0 skips it).
+With --full, the default weak scaling and N > 1 the same run also times the strong
+configuration (ImageNet.conf's global batch of 256 over the N ranks) and reports it as the
+nested "strong" record of the one JSON line (--strong-record 0 skips it).
 
 Data is synthetic 3x227x227 batches resident on the device with random-init weights (no
 dataset / checkpoint on the box).  By default they are uint8 HWC images -- what the
@@ -53,8 +58,15 @@ def _args(argv=None):
     ap.add_argument("--batch", type=int, default=256,
                     help="weak: per-GPU batch; strong: global batch split over the ranks")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every further measurement of this benchmark (today: the nested \"strong\" "
+                         "record at N > 1); a plain run times the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what a step of the timed path computes from the seeded "
+                         "initial state (the loss layer's fp32 scores, the updated parameters and their change) "
+                         "as DIR/<name>.npy, float32, <= 64 MB in all")
     ap.add_argument("--strong-record", type=int, default=1,
-                    help="with --scaling weak and N > 1, also time the conf's own configuration (global "
+                    help="with --full, --scaling weak and N > 1, also time the conf's own configuration (global "
                          "batch --batch split over the ranks, strong scaling) and add it as a nested "
                          "\"strong\" record to the one JSON line")
     ap.add_argument("--model", default="alexnet")
@@ -74,7 +86,12 @@ def _args(argv=None):
                     help="cpu: gloo ranks on the host (test hook for the launcher and the DP path)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VAL",
                     help="extra conf overrides, e.g. --set dp_comm_dtype=bf16")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def _free_port():
@@ -108,9 +125,10 @@ def _baseline(model):
 
 
 
-def _measure(a, world, rank, dev, global_batch, local_batch):
+def _measure(a, world, rank, dev, global_batch, local_batch, dump=False):
     """Build the trainer at (global_batch, local_batch), run a.warmup untimed steps, then time
-    a.steps steps bracketed by a barrier + device synchronisation; returns the MAX over ranks."""
+    a.steps steps bracketed by a barrier + device synchronisation; returns the MAX over ranks.
+    dump: also hand back the batch and a copy of the initial parameters for _dump_outputs."""
     import torch
     import torch.distributed as dist
     from cxxnet_amd.models import load_conf
@@ -131,6 +149,8 @@ def _measure(a, world, rank, dev, global_batch, local_batch):
         tr.set_param(k, v)
     tr.init_model()
     assert tr._local_batch() == local_batch, (tr._local_batch(), local_batch)
+    # --dump-outputs restarts from the seeded initial parameters (_dump_outputs)
+    w0 = tr.net.arena.w.clone() if dump else None
     c, h, w = tr.net_cfg.input_shape
     g = torch.Generator(device="cpu").manual_seed(1234 + rank)
     if a.input == "u8":
@@ -171,7 +191,7 @@ def _measure(a, world, rank, dev, global_batch, local_batch):
         dist.all_gather(allt, t)
         per_rank = [float(x.item()) for x in allt]
         el = max(per_rank)
-    return el, per_rank, tr, c, h, w, desc
+    return el, per_rank, tr, c, h, w, desc, batch, w0
 
 
 def _dp_info(tr):
@@ -182,6 +202,74 @@ def _dp_info(tr):
             "fullc_gather": any(getattr(c.layer, "_gathering", None) is not None and c.layer._gathering()
                                 for c in tr.net.connections),
             "overlapped_update": red.handles_update}
+
+
+DUMP_BUDGET = 6 << 20   # values per kind (param_*, step_*) written by --dump-outputs: 2 x 24 MB of float32
+SCORE_BUDGET = 2 << 20  # score values over all ranks: 8 MB (AlexNet b256 on 8 GPUs fits whole)
+DUMP_STEPS = 3          # steps from the initial state to the dumped one: the third has momentum behind it
+assert (2 * DUMP_BUDGET + SCORE_BUDGET) * 4 <= 64 << 20
+
+
+def _dump_outputs(tr, batch, w0, out_dir, rank, world):
+    """What a step of the timed path hands back, as float32 <name>.npy files under out_dir.
+
+    The state after the timed steps cannot be compared between two runs: the step sums fp32
+    gradients with atomics, so runs differ in the last bit, and bf16 training amplifies that
+    from step to step (profiles/bench_dump_repeatability.md).  So the dumped step is made
+    independent of how many steps ran before it: NetTrainer.reset_to puts the parameters back to
+    their seeded initial values (w0) and the optimizer state and counters to zero, and the timed
+    path -- the same trainer, batch, plans and tuned tiles -- runs DUMP_STEPS more steps.  The
+    last of them is written:
+      scores.npy (scores_rank<r>.npy on ranks > 0)  the loss layer's fp32 scores of this rank's rows
+                                                    (the first rows that fit SCORE_BUDGET / world);
+      param_<layer index>_<layer name>_<tag>.npy    from rank 0, every parameter after the update
+                                                    (the layout get_weight returns);
+      step_<layer index>_<layer name>_<tag>.npy     the same elements minus their initial values:
+                                                    what the DUMP_STEPS updates added, which a
+                                                    comparison of the parameters alone would not
+                                                    resolve (it is ~1e-3 of their range).
+    (Shapes missing from the shipped GEMM tile table are timed on first use, so two runs may run
+    different kernels: only dumps of shapes the table holds repeat to the last bits.)
+    Each kind shares DUMP_BUDGET values: a tensor over the common cap is written as a fixed sample
+    (indices drawn with a seed that depends only on the tensor's place in the net), so two builds
+    write the same elements."""
+    import numpy as np
+    import torch
+    net = tr.net
+    tr.reset_to(w0)
+    for _ in range(DUMP_STEPS):
+        tr.update(batch, local=True)
+    tr.prepare_save()  # (collective under sharded data parallelism: every rank calls it)
+    tr.reducer.sync()
+    os.makedirs(out_dir, exist_ok=True)
+    scores = tr._node_output(len(net.nodes) - 1)[: tr._rows]
+    scores = scores.reshape(scores.shape[0], -1)
+    scores = scores[: SCORE_BUDGET // world // max(scores.shape[1], 1)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, "scores.npy" if rank == 0 else f"scores_rank{rank}.npy"), scores)
+    if rank != 0:
+        return
+    specs = list(net.arena.specs)
+    sizes = sorted(s.numel for _, s in specs)
+    cap, left = (sizes[-1] if sizes else 0), DUMP_BUDGET
+    for i, n in enumerate(sizes):  # the largest cap with sum(min(numel, cap)) <= DUMP_BUDGET
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    for li, s in specs:
+        layer = net.connections[li].layer
+        w = s.w.detach().float()
+        d = w - w0[s.offset:s.offset + s.numel].view(s.shape)
+        name = f"{li:03d}_{tr.net_cfg.layers[li].name or 'layer'}_{s.tag}.npy"
+        for kind, t in (("param", w), ("step", d)):
+            t = t.cpu()
+            if hasattr(layer, "to_logical") and s.tag == "wmat":
+                t = layer.to_logical(t)  # (may drop channel padding: fewer values than s.numel)
+            t = t.reshape(-1)
+            if t.numel() > cap:
+                g = torch.Generator(device="cpu").manual_seed(7919 * li + (s.tag != "wmat"))
+                t = t[torch.randint(0, t.numel(), (cap,), generator=g)]
+            np.save(os.path.join(out_dir, f"{kind}_{name}"), t.numpy())
 
 
 def main():
@@ -213,13 +301,17 @@ def main():
         global_batch = a.batch
         local_batch = (a.batch + world - 1) // world
 
-    el, per_rank, tr, c, h, w, desc = _measure(a, world, rank, dev, global_batch, local_batch)
+    el, per_rank, tr, c, h, w, desc, batch, w0 = _measure(a, world, rank, dev, global_batch, local_batch,
+                                                          dump=bool(a.dump_outputs))
     ms = el / a.steps * 1000.0
     value = global_batch * a.steps / el
     base = _baseline(a.model)
     dp = _dp_info(tr)
+    if a.dump_outputs:
+        _dump_outputs(tr, batch, w0, a.dump_outputs, rank, world)
+        del batch, w0
     strong = None
-    if a.scaling == "weak" and world > 1 and a.strong_record:
+    if a.full and a.scaling == "weak" and world > 1 and a.strong_record:
         # the conf's own configuration: its global batch split over the ranks
         del tr
         if dev.type == "cuda":
@@ -231,6 +323,8 @@ def main():
                   "per_rank_ms_per_step": [round(x / a.steps * 1000.0, 3) for x in sper], "dp": _dp_info(str_)}
     elif a.scaling == "weak" and world == 1:
         strong = "identical to the weak record at one GPU (global batch = per-GPU batch)"
+    elif a.scaling == "weak" and a.strong_record:
+        strong = "not measured (a run with --full times it)"
     if rank == 0:
         name = MODEL_NAMES.get(a.model, a.model)
         out = {

@@ -387,6 +387,25 @@ class NetTrainer:
         self.net.arena.sync_shadow()
 
     # ------------------------------------------------------------------ training
+    def reset_to(self, w0: torch.Tensor):
+        """Put the training state back to a fresh start from the parameters w0 (a copy of
+        net.arena.w, e.g. taken right after init_model): parameters and their bf16 shadow,
+        optimizer state zeroed, update / micro-batch counters and the device step counter that
+        keys dropout at zero.  Buffers are written in place, so recorded launch lists and captured
+        graphs stay valid.  Every rank calls it with the same w0.  Whatever state a training step
+        carries to the next one belongs in here (bench.py --dump-outputs relies on it)."""
+        a = self.net.arena
+        self.reducer.sync()
+        if a.w.is_cuda:
+            torch.cuda.synchronize()
+        a.w.copy_(w0)
+        a.reset_state()
+        a.sync_shadow()
+        self.net.ctx.step_counter.zero_()
+        self.epoch_counter = self.sample_counter = 0
+        self._nf_flag = None
+        self.train_metric.clear()
+
     def start_round(self, r: int):
         self.net.start_round(r)
         # every rank calls start_round at the same point: adopt one tile choice for whatever any

@@ -105,6 +105,17 @@ def test_reference_confs_parse(path):
     assert c.num_layers > 3 and c.init_end == 1
 
 
+@pytest.mark.parametrize("path", ["imagenet/alexnet.conf", "imagenet/googlenet.conf", "mnist/mlp.conf",
+                                  "mnist/conv.conf", "kaggle_bowl/bowl.conf"])
+def test_example_confs_parse(path):
+    """The project's own example confs (examples/), which need nothing outside the repository."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    kv = rt().parse_config_file(os.path.join(root, "examples", path))
+    c = rt().NetConfig()
+    c.configure(kv)
+    assert c.num_layers > 3 and c.init_end == 1
+
+
 def test_layer_param_pod():
     p = rt().LayerParam()
     assert len(p.to_bytes()) == 328
