@@ -68,7 +68,7 @@ def case(N, C, Wp, out):
     tf = timeit(lambda: G.conv_forward(x, w, None, y, g))
     tw = timeit(lambda: G.conv_backward_weight(x, dyn, dw, g))
     for t in TILES:
-        G._TUNE["|".join(str(v) for v in ("cr", N, H, Wp, C, 96, 11, 11, 4))] = t
+        G._TUNE[G.sig("cr", N, H, Wp, C, 96, 11, 11, 4)] = t
         y.zero_()
         G.conv_forward(x, w, None, y, g)
         torch.cuda.synchronize()

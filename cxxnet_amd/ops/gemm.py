@@ -14,6 +14,7 @@ src/layer/fullc_layer-inl.hpp:101-130.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 from dataclasses import dataclass
 
@@ -21,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import native
-from .mode import frozen, native as _native_t
+from .mode import frozen, native as _native_t, workspace
 
 DIRECT_K, DIRECT_MN, GATHER_K, GATHER_MN = 0, 1, 2, 3
 EPI_BF16, EPI_F32, EPI_F32_ACC, EPI_F32_ATOMIC = 0, 1, 2, 3
@@ -125,6 +126,15 @@ FC_TILES = (0, 5, 1)
 
 def _cdiv(a, b):
     return -(-a // b)
+
+
+def served(rc, what) -> bool:
+    """The library's return convention: 0 done, -1 shape not served (the caller falls back), any
+    other code an error."""
+    if rc == -1:
+        return False
+    native.check(rc, what)
+    return True
 
 
 def _pick(candidates, rows_i, rows_j, groups, min_blocks=2 * NUM_CU):
@@ -278,10 +288,51 @@ def _agrees(a: torch.Tensor, ref: torch.Tensor, tol: float = 2e-2) -> float:
     return (a - ref).norm().item() / max(den, 1e-30)
 
 
-def _tuned_tile(key, run, out, default, extra=(), tune=True, cands=None):
-    """Tile for a GEMM signature: the fastest candidate, timed once per process on a
-    scratch output (the first call of each shape pays a few extra launches and one host
-    sync); the heuristic pick when tuning is off or a graph is being captured.
+_CONV_FIELDS = ("N", "H", "W", "C", "Cout", "KH", "KW", "stride", "pad_y", "pad_x", "groups")
+# what identifies a shape, per op class of the tile table (the conv classes: ConvGeom attributes;
+# the row-run kernels serve pad 0, one group only)
+SIG_FIELDS = {"cf": _CONV_FIELDS, "cd": _CONV_FIELDS, "cw": _CONV_FIELDS, "cws": _CONV_FIELDS,
+              "cr": _CONV_FIELDS[:8], "cwr": _CONV_FIELDS[:8], "cfs": ("N", "H", "W", "C", "Cout", "split"),
+              "fc": ("amode", "rows_a", "rows_b", "kdim", "ldc"), "fw": ("nin", "nout", "batch"),
+              "fws": ("nin", "nout", "batch")}
+
+
+def sig(op, *fields) -> str:
+    """Key of the tile table: the op class and its SIG_FIELDS values."""
+    return "|".join(map(str, (op,) + fields))
+
+
+_GEOM_FIELDS = {op: operator.attrgetter(*SIG_FIELDS[op]) for op in ("cf", "cd", "cw", "cws", "cr", "cwr")}
+
+
+def _conv_sig(op, g: ConvGeom) -> str:
+    return sig(op, *_GEOM_FIELDS[op](g))
+
+
+def _may_tune() -> bool:
+    return _glds_cfg["tune"] and not frozen()
+
+
+def _tile(key, default=None, run=None, out=None, extra=(), cands=None, tune=True, own_ids=False):
+    """Tile of signature `key`: the forced tile, else the table's, else timed on first use
+    (_tuned_tile with run / out / extra / cands), else default().  Without `run` it only looks
+    up (epilogues that accumulate into the live buffer or update weights are never timed); without
+    `default` a miss is None.  own_ids: the signature's ids are not LDS-DMA tiles, so a forced
+    tile means default() here."""
+    if _glds_cfg["tile"] >= 0:
+        return default() if own_ids else _glds_cfg["tile"]
+    t = _TUNE.get(key)
+    if t is not None:
+        return t
+    if run is not None and tune and _may_tune():
+        return _tuned_tile(key, run, out, default, extra, cands)
+    return default() if default is not None else None
+
+
+def _tuned_tile(key, run, out, default, extra=(), cands=None):
+    """The fastest candidate tile for signature `key` (a sig() string, or its (op, *fields)
+    tuple), timed once per process on a scratch output (the first call of each shape pays a few
+    extra launches and one host sync) and entered into the table.
 
     A candidate is eligible only if its output agrees with the heuristic tile's output on
     the same operands (norm-relative difference < 2e-2; bf16 rounding and split-K order
@@ -290,14 +341,8 @@ def _tuned_tile(key, run, out, default, extra=(), tune=True, cands=None):
     an unfenced intra-wave LDS hand-off in the epilogue, is fixed in gemm_glds.hip wave_lds_handoff).
     Scratch outputs start from the live output's contents, so masked (mask_relu) and
     accumulating epilogues see the same inputs for every candidate."""
-    if _glds_cfg["tile"] >= 0:
-        return _glds_cfg["tile"]
-    key = "|".join(str(k) for k in key)
-    t = _TUNE.get(key)
-    if t is not None:
-        return t
-    if not (tune and _glds_cfg["tune"]) or frozen():
-        return default()
+    if not isinstance(key, str):
+        key = sig(*key)
     if _TUNE_LOG:
         import sys
         print(f"gemm tune: timing {key} (not in the tile table)", file=sys.stderr, flush=True)
@@ -398,23 +443,20 @@ def _pick_glds(rows_i, rows_j, groups, nblocks_target=NUM_CU):
 
 
 def _glds(a, b, amode, bmode, out, out_gstride, ldc, *, alpha=1.0, bias=None, bias_gstride=0, relu=False,
-          mask_relu=False, epi=EPI_BF16, groups=1, ksplit=1, kstride=0, tile=None, dbias=None, dws=None,
+          mask_relu=False, epi=EPI_BF16, groups=1, ksplit=1, kstride=0, tile, dbias=None, dws=None,
           dws_ld=0) -> bool:
     """Run the LDS-DMA kernel; False when it does not support the operands (caller falls back)."""
     if not _glds_cfg["on"]:
         return False
-    if tile is None:
-        tile = _glds_cfg["tile"] if _glds_cfg["tile"] >= 0 else _pick_glds(a.rows, b.rows, groups)
     rc = native.kernels().cxn_gemm_glds(
         a, b, amode, bmode, out.data_ptr(), out_gstride, ldc, float(alpha),
         bias.data_ptr() if bias is not None else None, bias_gstride, int(relu), int(mask_relu), epi, tile, groups,
         ksplit, kstride, dbias.data_ptr() if dbias is not None else None,
         dws.data_ptr() if dws is not None else None, dws.numel() if dws is not None else 0, int(dws_ld), _stream())
-    if rc == -1:
-        return False
-    native.check(rc, "gemm_glds")
-    LAST_GLDS[0] = tile
-    return True
+    if served(rc, "gemm_glds"):
+        LAST_GLDS[0] = tile
+        return True
+    return False
 
 
 LAST_GLDS = [None]  # tile of the last LDS-DMA launch (tests check that a forced tile really ran)
@@ -488,14 +530,14 @@ def _gemm_bf16_out(a, b, amode, bmode, out, ldc, *, bias=None, relu=False, mask_
 def _fc_glds(a, b, amode, out, ldc, bias, relu, mask_relu, drop=None):
     """fc forward (A = W, K-major) / data-grad (A = W, MN-major) on the LDS-DMA kernel.  None
     when the kernel does not serve the shape; else whether the dropout (drop) was applied."""
-    key = ("fc", amode, a.rows, b.rows, a.kdim, ldc)
     got = {}
 
     def run(t, o):
         r = _fc_glds_tile(a, b, amode, o, ldc, bias, relu, mask_relu, t, drop)
         got["drop"] = r == 2
         return bool(r)
-    tile = _tuned_tile(key, run, out, lambda: 1 if amode == GL_MN else _pick_glds(a.rows, b.rows, 1))
+    tile = _tile(sig("fc", amode, a.rows, b.rows, a.kdim, ldc),
+                 lambda: 1 if amode == GL_MN else _pick_glds(a.rows, b.rows, 1), run, out)
     if not run(tile, out):
         return None
     return got["drop"]
@@ -584,16 +626,6 @@ def _row_padded_weights(w, g: ConvGeom):
 
 
 _wgpad = {}
-_detws = {}
-
-
-def _det_ws(n, device):
-    buf = _detws.get(str(device))
-    if buf is None or buf.numel() < n:
-        from .mode import retire
-        retire(buf)  # a recorded / captured step may still point at it
-        buf = _detws[str(device)] = torch.empty(n, dtype=torch.float32, device=device)
-    return buf[:n]
 
 
 def _add_rows(src, dst, rows, L, Ls):
@@ -631,10 +663,7 @@ def conv_rowrun_fwd2(x, w, bias, y, g: ConvGeom, relu=False) -> bool:
     rc = native.kernels().cxn_conv_rowrun_fwd2(
         x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), g.N, g.H, g.W,
         g.C, g.Ho, g.Wo, g.Cout, _pix(y), g.KH, g.KW, g.stride, g.pad_y, int(relu), _stream())
-    if rc == -1:
-        return False
-    native.check(rc, "conv_rowrun_fwd2")
-    return True
+    return served(rc, "conv_rowrun_fwd2")
 
 
 def fewc_ok(x, g: ConvGeom) -> bool:
@@ -658,10 +687,55 @@ def conv_forward_fewc(x, w, bias, y, g: ConvGeom, relu=False) -> bool:
     rc = native.kernels().cxn_conv_fewc_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                            y.data_ptr(), g.N, g.H, g.W, g.Ho, g.Wo, g.Cout, g.KH, g.KW, g.stride,
                                            g.pad_y, _pix(y), int(relu), _stream())
-    if rc == -1:
-        return False
-    native.check(rc, "conv_fewc_fwd")
-    return True
+    return served(rc, "conv_fewc_fwd")
+
+
+def _fwd_operands(x, w, g: ConvGeom):
+    """The forward implicit GEMM: A = the weights ([cg_out][kdim] per group), B = the im2col gather
+    of x.  B's C is the input's pixel stride: a channel slice of a wider buffer (sibling outputs,
+    NeuralNet._fuse_siblings) is read in place."""
+    cg, kd = g.cg_in, g.kdim
+    A = _op(w, g.cg_out * kd, kd, g.cg_out, kd)
+    B = _op(x, cg, 0, g.N * g.Ho * g.Wo, kd, H=g.H, W=g.W, C=_pix(x), Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW,
+            stride=g.stride, pad_h=g.pad_y, pad_w=g.pad_x, dil=1, Cg=cg)
+    return A, B
+
+
+def _dgrad_operands(dy, w, wt_buf, g: ConvGeom, wt_ready):
+    """The data-gradient implicit GEMM: A = the flipped weights (written into wt_buf here unless
+    wt_ready), B = the gather of dy as a stride-1 convolution with full padding, dilated by the
+    forward stride."""
+    cg_in, cg_out = g.cg_in, g.cg_out
+    if not wt_ready:
+        native.check(native.kernels().cxn_conv_weight_flip(w.data_ptr(), wt_buf.data_ptr(), g.groups, cg_out, g.KH,
+                                                           g.KW, cg_in, _stream()), "conv_weight_flip")
+    kd = g.KH * g.KW * cg_out
+    A = _op(wt_buf, cg_in * kd, kd, cg_in, kd)
+    B = _op(dy, cg_out, 0, g.N * g.H * g.W, kd, H=g.Ho, W=g.Wo, C=_pix(dy), Ho=g.H, Wo=g.W, KH=g.KH,
+            KW=g.KW, stride=1, pad_h=g.KH - 1 - g.pad_y, pad_w=g.KW - 1 - g.pad_x, dil=g.stride, Cg=cg_out)
+    return A, B
+
+
+def _wgrad_operands(x, dy, g: ConvGeom):
+    """The weight-gradient GEMM over the pixels: A = the transposed im2col gather of x, B = dy."""
+    cg, P = g.cg_in, g.N * g.Ho * g.Wo
+    A = _op(x, cg, 0, g.kdim, P, H=g.H, W=g.W, C=_pix(x), Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW, stride=g.stride,
+            pad_h=g.pad_y, pad_w=g.pad_x, dil=1, Cg=cg)
+    B = _op(dy, g.cg_out, _pix(dy), g.cg_out, P)
+    return A, B
+
+
+def _run_tile(key, run, out, pick, extra, *live):
+    """The "cf" / "cd" dispatch: run(tile, out, *live) with the signature's tile (_tile; the
+    tuner's candidates are GLDS_CANDS + extra, on scratch outputs without `live`).  When that is
+    a direct pseudo-tile (DIRECT_TILES) and the direct kernel is switched off or refuses, the
+    LDS-DMA GEMM of the heuristic tile pick() runs instead, with the same epilogue.  Returns
+    run's result; falsy: nothing ran and the caller's register kernel is next."""
+    t = _tile(key, pick, run, out, extra)
+    r = run(t, out, *live)
+    if not r and t in DIRECT_TILES:
+        r = run(pick(), out, *live)
+    return r
 
 
 def conv_forward(x, w, bias, y, g: ConvGeom, relu=False):
@@ -679,12 +753,8 @@ def conv_forward(x, w, bias, y, g: ConvGeom, relu=False):
         return
     if cg % va and not rowrun_ok(g):
         raise ValueError(f"conv: channels per group ({cg}) must be a multiple of 4 on the GPU path")
-    kd = g.kdim
-    A = _op(w, g.cg_out * kd, kd, g.cg_out, kd)
-    # C = the input's pixel stride: a channel slice of a wider buffer (sibling outputs,
-    # NeuralNet._fuse_siblings) is read in place
-    B = _op(x, cg, 0, g.N * g.Ho * g.Wo, kd, H=g.H, W=g.W, C=_pix(x), Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW,
-            stride=g.stride, pad_h=g.pad_y, pad_w=g.pad_x, dil=1, Cg=cg)
+    A, B = _fwd_operands(x, w, g)
+
     def reg(o):
         tile = _pick(CONV_FWD_TILES if va == 8 else CONV_FWD_TILES_V4, g.cg_out, g.N * g.Ho * g.Wo, g.groups)
         _gemm(A, B, DIRECT_K, GATHER_K, va, va, o, g.cg_out, _pix(o), bias=bias, bias_gstride=g.cg_out, relu=relu,
@@ -698,34 +768,27 @@ def conv_forward(x, w, bias, y, g: ConvGeom, relu=False):
                 return _CD != "0" and conv_direct_forward(x, w, bias, o, g, relu=relu, variant=DIRECT_TILES[t])
             return _glds(A, B, GL_K, GL_KG, o, g.cg_out, _pix(o), bias=bias, bias_gstride=g.cg_out, relu=relu,
                          groups=g.groups, tile=t)
-        key = ("cf", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride, g.pad_y, g.pad_x, g.groups)
         extra = (REG,) + (tuple(DIRECT_TILES) if _cd_serves(g, x, y) else ())
-        t = _tuned_tile(key, run, y, lambda: _pick_glds(A.rows, B.rows, g.groups), extra=extra)
-        if run(t, y):
-            return
-        if t in DIRECT_TILES and run(_pick_glds(A.rows, B.rows, g.groups), y):  # (direct kernel switched off)
+        if _run_tile(_conv_sig("cf", g), run, y, lambda: _pick_glds(A.rows, B.rows, g.groups), extra):
             return
     if va != 8 and rowrun_ok(g) and (_use("cr") or g.C % 4):
         # few input channels (conv1: 11x11 taps of 4 channels): each kernel row's KW*C
         # elements are contiguous in NHWC; the GEMM reads them as zero-padded runs
-        if conv_rowrun_fwd2(x, w, bias, y, g, relu):
+        if g.C != 4 and conv_rowrun_fwd2(x, w, bias, y, g, relu):  # (4 channels: tried above)
             return
         wp, lp = _row_padded_weights(w, g)
         if _ROWRUN_DIRECT and x.is_contiguous() and y.shape[-1] == _pix(y):
             rc = native.kernels().cxn_conv_rowrun_fwd(
                 x.data_ptr(), x.numel() * x.element_size(), wp.data_ptr(), bias.data_ptr() if bias is not None else None,
                 y.data_ptr(), g.N, g.H, g.W, g.C, g.Ho, g.Wo, g.Cout, g.KH, lp, g.stride, _pix(y), int(relu), _stream())
-            if rc == 0:
+            if served(rc, "conv_rowrun_fwd"):
                 return
-            if rc != -1:
-                native.check(rc, "conv_rowrun_fwd")
         kr = g.KH * lp
         Ar = _op(wp, 0, kr, g.Cout, kr)
         Br = _op(x, 0, 0, g.N * g.Ho * g.Wo, kr, H=g.H, W=g.W, C=g.C, Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW,
                  stride=g.stride, pad_h=0, pad_w=0, dil=1, Cg=g.C)
         run = lambda t, o: _glds(Ar, Br, GL_K, GL_KR, o, 0, _pix(o), bias=bias, relu=relu, tile=t)  # noqa: E731
-        key = ("cr", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride)
-        if run(_tuned_tile(key, run, y, lambda: 1), y):
+        if run(_tile(_conv_sig("cr", g), lambda: 1, run, y), y):
             return
     if cg % va:
         raise RuntimeError(f"conv: no GPU kernel for {cg} channels per group ({g})")
@@ -746,11 +809,7 @@ def conv_forward_split(x, w, bias, y, y2, split, g: ConvGeom, relu=False):
         y.copy_(t[..., :split])
         y2.copy_(t[..., split:])
         return
-    cg = g.cg_in
-    kd = g.kdim
-    A = _op(w, g.cg_out * kd, kd, g.cg_out, kd)
-    B = _op(x, cg, 0, g.N * g.Ho * g.Wo, kd, H=g.H, W=g.W, C=_pix(x), Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW,
-            stride=g.stride, pad_h=g.pad_y, pad_w=g.pad_x, dil=1, Cg=cg)
+    A, B = _fwd_operands(x, w, g)
 
     def run(t, o):
         if t == REG or not _glds_cfg["on"]:
@@ -758,14 +817,13 @@ def conv_forward_split(x, w, bias, y, y2, split, g: ConvGeom, relu=False):
         rc = native.kernels().cxn_gemm_glds_split(
             A, B, GL_K, GL_KG, o.data_ptr(), _pix(o), y2.data_ptr(), _pix(y2), int(split),
             bias.data_ptr() if bias is not None else None, int(relu), t, _stream())
-        if rc == -1:
-            return False
-        native.check(rc, "gemm_glds_split")
-        LAST_GLDS[0] = t
-        return True
-    key = ("cfs", g.N, g.H, g.W, g.C, g.Cout, split)
-    if cg % 8 == 0 and g.groups == 1 and _use("cf"):
-        t = _tuned_tile(key, run, y, lambda: _pick_glds(A.rows, B.rows, 1), cands=SPLIT_CANDS)
+        if served(rc, "gemm_glds_split"):
+            LAST_GLDS[0] = t
+            return True
+        return False
+    if g.cg_in % 8 == 0 and g.groups == 1 and _use("cf"):
+        t = _tile(sig("cfs", g.N, g.H, g.W, g.C, g.Cout, split), lambda: _pick_glds(A.rows, B.rows, 1), run, y,
+                  cands=SPLIT_CANDS)
         if run(t, y):
             return
     # no two-destination tile for this shape: the two channel ranges as two GEMMs
@@ -805,18 +863,13 @@ def conv_backward_data(dy, w, dx, g: ConvGeom, wt_buf=None, mask_relu=False, wt_
             out = out * (dx > 0).to(out.dtype)
         dx.copy_(out)
         return False
-    cg_in, cg_out = g.cg_in, g.cg_out
-    if cg_out % 8:
+    cg_in = g.cg_in
+    if g.cg_out % 8:
         raise ValueError("conv dgrad: output channels per group must be a multiple of 8 on the GPU path")
     if wt_buf is None:
         wt_buf = torch.empty_like(w)
-    if not wt_ready:
-        native.check(native.kernels().cxn_conv_weight_flip(w.data_ptr(), wt_buf.data_ptr(), g.groups, cg_out, g.KH,
-                                                           g.KW, cg_in, _stream()), "conv_weight_flip")
-    kd = g.KH * g.KW * cg_out
-    A = _op(wt_buf, cg_in * kd, kd, cg_in, kd)
-    B = _op(dy, cg_out, 0, g.N * g.H * g.W, kd, H=g.Ho, W=g.Wo, C=_pix(dy), Ho=g.H, Wo=g.W, KH=g.KH,
-            KW=g.KW, stride=1, pad_h=g.KH - 1 - g.pad_y, pad_w=g.KW - 1 - g.pad_x, dil=g.stride, Cg=cg_out)
+    A, B = _dgrad_operands(dy, w, wt_buf, g, wt_ready)
+
     def reg(o):
         tile = _pick(CONV_FWD_TILES, cg_in, g.N * g.H * g.W, g.groups)
         _gemm(A, B, DIRECT_K, GATHER_K, 8, 8, o, cg_in, _pix(o), epi=EPI_BF16, groups=g.groups, mask_relu=mask_relu,
@@ -825,29 +878,28 @@ def conv_backward_data(dy, w, dx, g: ConvGeom, wt_buf=None, mask_relu=False, wt_
     if g.stride == 1 and _use("cd"):
         dg = ConvGeom(g.N, g.H, g.W, g.Cout, g.H, g.W, g.C, g.KH, g.KW, 1, g.pad_y, g.pad_x, g.groups)
 
-        def run(t, o):
+        def run(t, o, db=None):
+            """0: not served, 1: o written, 2: o written and db accumulated."""
             if t == REG:
                 return reg(o)
             if t in DIRECT_TILES:
-                return _CD != "0" and conv_direct_data(dy, wt_buf, o, g, mask_relu=mask_relu,
-                                                       variant=DIRECT_TILES[t])
+                if deterministic():
+                    db = None
+                if _CD != "0" and conv_direct_data(dy, wt_buf, o, g, mask_relu=mask_relu, dbias=db,
+                                                   variant=DIRECT_TILES[t]):
+                    return 2 if db is not None else 1
+                return 0
+            if db is not None and (t not in (130, 131) or _HALO_DB):
+                from .nn import _workspace
+                ws = _workspace((-(-B.rows // 16) + 8) * g.C, o.device)  # >= tiles_j * waves_j rows
+                if _glds(A, B, GL_K, GL_KG, o, cg_in, _pix(o), groups=g.groups, mask_relu=mask_relu, tile=t,
+                         epi=EPI_BF16_DB_G, bias_gstride=cg_in, dbias=db, dws=ws, dws_ld=g.C):
+                    return 2
             return _glds(A, B, GL_K, GL_KG, o, cg_in, _pix(o), groups=g.groups, mask_relu=mask_relu, tile=t)
-        key = ("cd", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride, g.pad_y, g.pad_x, g.groups)
         extra = (REG,) + (tuple(DIRECT_TILES) if _cd_serves(dg, dy, dx) else ())
-        t = _tuned_tile(key, run, dx, lambda: _pick_glds(A.rows, B.rows, g.groups), extra=extra)
-        if t in DIRECT_TILES and _CD != "0":
-            db = dbias if dbias is not None and not deterministic() else None
-            if conv_direct_data(dy, wt_buf, dx, g, mask_relu=mask_relu, dbias=db, variant=DIRECT_TILES[t]):
-                return db is not None
-            t = _pick_glds(A.rows, B.rows, g.groups)
-        if dbias is not None and t != REG and (t not in (130, 131) or _HALO_DB):
-            from .nn import _workspace
-            ws = _workspace((-(-B.rows // 16) + 8) * g.C, dx.device)  # >= tiles_j * waves_j rows
-            if _glds(A, B, GL_K, GL_KG, dx, cg_in, _pix(dx), groups=g.groups, mask_relu=mask_relu, tile=t,
-                     epi=EPI_BF16_DB_G, bias_gstride=cg_in, dbias=dbias, dws=ws, dws_ld=g.C):
-                return True
-        if run(t, dx):
-            return False
+        r = _run_tile(_conv_sig("cd", g), run, dx, lambda: _pick_glds(A.rows, B.rows, g.groups), extra, dbias)
+        if r:
+            return r == 2
     reg(dx)
     return False
 
@@ -862,52 +914,32 @@ def conv_backward_data_add(dy, w, dx, add, g: ConvGeom, wt_buf, mask_relu=False,
         return False
     if tuple(add.shape) != tuple(dx.shape) or not _glds_cfg["on"]:
         return False
-    key = "|".join(str(k) for k in ("cd", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride, g.pad_y, g.pad_x,
-                                    g.groups))
-    cg_in, cg_out = g.cg_in, g.cg_out
-    kd = g.KH * g.KW * cg_out
-    A = _op(wt_buf, cg_in * kd, kd, cg_in, kd)
-    B = _op(dy, cg_out, 0, g.N * g.H * g.W, kd, H=g.Ho, W=g.Wo, C=_pix(dy), Ho=g.H, Wo=g.W, KH=g.KH,
-            KW=g.KW, stride=1, pad_h=g.KH - 1 - g.pad_y, pad_w=g.KW - 1 - g.pad_x, dil=g.stride, Cg=cg_out)
-    t = _glds_cfg["tile"] if _glds_cfg["tile"] >= 0 else _TUNE.get(key)
+    t = _tile(_conv_sig("cd", g))
     if t is None:  # not tuned yet: the plain path tunes it; with tuning off, its default pick
-        if _glds_cfg["tune"] and not frozen():
+        if _may_tune():
             return False
-        t = _pick_glds(A.rows, B.rows, g.groups)
+        t = _pick_glds(g.cg_in, g.N * g.H * g.W, g.groups)
     if t == REG or t == 114 or 130 <= t <= 142:
         return False
-    if not wt_ready:
-        native.check(native.kernels().cxn_conv_weight_flip(w.data_ptr(), wt_buf.data_ptr(), g.groups, cg_out, g.KH,
-                                                           g.KW, cg_in, _stream()), "conv_weight_flip")
-    rc = native.kernels().cxn_gemm_glds_add(A, B, GL_K, GL_KG, dx.data_ptr(), cg_in, _pix(dx), add.data_ptr(),
+    A, B = _dgrad_operands(dy, w, wt_buf, g, wt_ready)
+    rc = native.kernels().cxn_gemm_glds_add(A, B, GL_K, GL_KG, dx.data_ptr(), g.cg_in, _pix(dx), add.data_ptr(),
                                             int(mask_relu), t, g.groups, _stream())
-    if rc == -1:  # (a flip done here is repeated by the caller's path: the same values)
-        return False
-    native.check(rc, "gemm_glds_add")
-    LAST_GLDS[0] = t
-    return True
+    if served(rc, "gemm_glds_add"):  # (else a flip done here is repeated by the caller's path: the same values)
+        LAST_GLDS[0] = t
+        return True
+    return False
 
 
 # Direct small-map forward / data gradient (conv_direct.hip: gap-slot layout, taps as constant
 # LDS offsets, persistent blocks).  "auto" / "1": wherever it serves the shape; "0": off (the
 # implicit GEMMs run).
 _CD = os.environ.get("CXXNET_CONV_DIRECT", "auto")
-_cd_ws = {}
 # Pseudo-tiles of the tile table for the direct kernel's schedules (cxn_conv_direct variant):
 # 200 persistent blocks with two stage buffers, 201 one block per item (two per CU), 202 as 200
 # with four LDS-DMA loader waves per block, 203 version 2 (eight waves, two per SIMD, paired taps,
 # persistent double-buffered stages).  Tuning candidates of the "cf" / "cd" signatures it
 # serves (in-step picks at the strong-scaling batches: profiles/r6_step_tune_direct_b{32,64,128}.jsonl).
 DIRECT_TILES = {200: 0, 201: 1, 202: 2, 203: 3}
-
-
-def _cd_workspace(n, device):
-    buf = _cd_ws.get(str(device))
-    if buf is None or buf.numel() < n:
-        from .mode import retire
-        retire(buf)
-        buf = _cd_ws[str(device)] = torch.empty(max(n, 1 << 16), dtype=torch.float32, device=device)
-    return buf
 
 
 def _cd_ok(g: ConvGeom, *ts) -> bool:
@@ -936,10 +968,7 @@ def conv_direct_forward(x, w, bias, y, g: ConvGeom, relu=False, variant=0) -> bo
     rc = int(native.kernels().cxn_conv_direct(
         x.data_ptr(), _pix(x), w.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), _pix(y),
         None, 0, None, g.N, g.H, g.W, g.cg_in, g.cg_out, g.groups, g.KH, int(relu), 0, int(variant), _stream()))
-    if rc == -1:
-        return False
-    native.check(rc, "conv_direct")
-    return True
+    return served(rc, "conv_direct")
 
 
 def conv_direct_data(dy, wt, dx, g: ConvGeom, mask_relu=False, dbias=None, variant=0) -> bool:
@@ -954,32 +983,23 @@ def conv_direct_data(dy, wt, dx, g: ConvGeom, mask_relu=False, dbias=None, varia
         need = int(k.cxn_conv_direct(None, _pix(dy), None, None, None, _pix(dx), None, 0, None, *args, 2, 0, None))
         if need <= 0:
             return False
-        ws = _cd_workspace(need, dx.device)
+        ws = workspace("conv_direct", need, dx.device, 1 << 16)
         n = ws.numel()
     rc = int(k.cxn_conv_direct(dy.data_ptr(), _pix(dy), wt.data_ptr(), None, dx.data_ptr(), _pix(dx),
                                ws.data_ptr() if ws is not None else None, n,
                                dbias.data_ptr() if dbias is not None else None, *args,
                                2 if dbias is not None else 1, int(variant), _stream()))
-    if rc == -1:
-        return False
-    native.check(rc, "conv_direct")
-    return True
+    return served(rc, "conv_direct")
 
 
 # Direct small-map weight gradient (conv_wgrad_direct.hip: gap-slot K walk, resident x / dy
 # stages, partial tiles reduced in a fixed order -- no atomics, deterministic).  "1" / "auto":
 # use it wherever it serves the shape; "0": off (the split-K GEMMs run).
 _WGD = os.environ.get("CXXNET_WGRAD_DIRECT", "auto")
-_wgd_ws = {}
 
 
 def _wgd_workspace(n, device):
-    buf = _wgd_ws.get(str(device))
-    if buf is None or buf.numel() < n:
-        from .mode import retire
-        retire(buf)  # a recorded / captured step may still point at it
-        buf = _wgd_ws[str(device)] = torch.empty(max(n, 1 << 20), dtype=torch.float32, device=device)
-    return buf
+    return workspace("wgrad_direct", n, device, 1 << 20)
 
 
 def conv_wgrad_direct(x, dy, dw, g: ConvGeom, splits: int = 0, db=None) -> bool:
@@ -999,10 +1019,7 @@ def conv_wgrad_direct(x, dy, dw, g: ConvGeom, splits: int = 0, db=None) -> bool:
     ws = _wgd_workspace(need, dw.device)
     rc = int(k.cxn_conv_wgrad_direct(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
                                      ws.data_ptr(), ws.numel(), *args, 1.0, _stream()))
-    if rc == -1:
-        return False
-    native.check(rc, "conv_wgrad_direct")
-    return True
+    return served(rc, "conv_wgrad_direct")
 
 
 def conv_wgrad_rowrun(x, dy, dw, g: ConvGeom) -> bool:
@@ -1021,10 +1038,7 @@ def conv_wgrad_rowrun(x, dy, dw, g: ConvGeom) -> bool:
     ws = _wgd_workspace(need, dw.device)
     rc = int(k.cxn_conv_wgrad_rowrun(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), *args, 1.0,
                                      _stream()))
-    if rc == -1:
-        return False
-    native.check(rc, "conv_wgrad_rowrun")
-    return True
+    return served(rc, "conv_wgrad_rowrun")
 
 
 def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
@@ -1045,9 +1059,7 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
     va = 8 if cg % 8 == 0 else 4
     kd = g.kdim
     P = g.N * g.Ho * g.Wo
-    A = _op(x, cg, 0, kd, P, H=g.H, W=g.W, C=_pix(x), Ho=g.Ho, Wo=g.Wo, KH=g.KH, KW=g.KW, stride=g.stride,
-            pad_h=g.pad_y, pad_w=g.pad_x, dil=1, Cg=cg)
-    B = _op(dy, g.cg_out, _pix(dy), g.cg_out, P)
+    A, B = _wgrad_operands(x, dy, g)
 
     def reg_run(code, o):
         _gemm(A, B, GATHER_MN, DIRECT_MN, va, 8, o, g.cg_out * kd, kd, epi=EPI_F32_ATOMIC, groups=g.groups,
@@ -1058,11 +1070,9 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
         tile = _pick(WGRAD_TILES, kd, g.cg_out, g.groups, min_blocks=1)
         return tile * 100000 + _auto_split(kd, g.cg_out, g.groups, P, tile)
 
-    def reg(o):
-        if _glds_cfg["tile"] >= 0:  # a forced LDS-DMA tile id means nothing here
-            return reg_run(reg_default(), o)
-        key = ("cws", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride, g.pad_y, g.pad_x, g.groups)
-        return reg_run(_tuned_tile(key, reg_run, o, reg_default, cands=_wgrad_cands(kd, g.cg_out, g.groups, P)), o)
+    def reg(o):  # ("cws" ids are tile * 100000 + slices: a forced LDS-DMA tile id means nothing here)
+        return reg_run(_tile(_conv_sig("cws", g), reg_default, reg_run, o, own_ids=True,
+                             cands=_wgrad_cands(kd, g.cg_out, g.groups, P)), o)
     rowrun = va != 8 and rowrun_ok(g)
     if conv_wgrad_direct(x, dy, dw, g, db=db):  # deterministic as well: no atomics, fixed split order
         return db is not None
@@ -1073,7 +1083,7 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
         tile = _pick(WGRAD_TILES, kd, g.cg_out, g.groups, min_blocks=1)
         split = _effective_split(P, _auto_split(kd, g.cg_out, g.groups, P, tile))
         slab = g.Cout * kd
-        ws = _det_ws(split * slab, dw.device)
+        ws = workspace("det_wgrad", split * slab, dw.device)[:split * slab]
         _gemm(A, B, GATHER_MN, DIRECT_MN, va, 8, ws, g.cg_out * kd, kd, epi=EPI_F32, groups=g.groups,
               ksplit=split, tile=tile, kstride=slab)
         native.check(native.kernels().cxn_splitk_accumulate(ws.data_ptr(), split, slab, dw.data_ptr(), _stream()),
@@ -1088,10 +1098,9 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
             split = max(1, min(2 * NUM_CU // max(tiles, 1), _cdiv(P, 64) // 16))
             return _glds(A, B, GL_MNG, GL_MN, o, g.cg_out * kd, kd, epi=EPI_F32_ATOMIC_G, groups=g.groups,
                          ksplit=split, tile=t)
-        key = ("cw", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride, g.pad_y, g.pad_x, g.groups)
         # shapes missing from the table keep the register kernel: timed alone, the LDS-DMA form
         # wins shapes where it loses inside the step (conv2/conv3 above)
-        if run(_tuned_tile(key, run, dw, lambda: REG, extra=(REG,), tune=_CW_TUNE), dw):
+        if run(_tile(_conv_sig("cw", g), lambda: REG, run, dw, tune=_CW_TUNE, extra=(REG,)), dw):
             return
     if rowrun and (_use("cwr") or g.C % 4 or _DET["on"]):
         # few input channels (conv1): the KW*C im2col rows of one kernel row are one contiguous run
@@ -1109,10 +1118,9 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
             if _DET["on"]:  # one K slice: each output is one atomic add onto zero, bitwise reproducible
                 split = 1
             return _glds(Ar, B, GL_MNG, GL_MN, o, 0, kr, epi=EPI_F32_ATOMIC_G, ksplit=split, tile=t)
-        key = ("cwr", g.N, g.H, g.W, g.C, g.Cout, g.KH, g.KW, g.stride)
         from .nn import zero_
         zero_(ws)  # library memset / add below: a replayed launch list repeats them (torch ops it would not)
-        if run(_tuned_tile(key, run, ws, lambda: 1), ws):
+        if run(_tile(_conv_sig("cwr", g), lambda: 1, run, ws), ws):
             _add_rows(ws, dw, g.Cout * g.KH, g.KW * g.C, lp)
             return
     if cg % va:
@@ -1185,18 +1193,13 @@ def fc_backward_weight_sgd(x, dy, w, m, wb, lr, wd, mom, clip, hyp=None) -> bool
     A = _op(x, 0, nin, nin, Bn)
     Bo = _op(dy, 0, nout, nout, Bn)
     # the SGD epilogue streams w / m / wb: its own tile entry ("fws"), else the plain weight-grad one
-    tile = _glds_cfg["tile"]
-    if tile < 0:
-        tile = _TUNE.get(f"fws|{nin}|{nout}|{Bn}")
-        if tile is None:
-            tile = _TUNE.get(f"fw|{nin}|{nout}|{Bn}", 1)
+    tile = _tile(sig("fws", nin, nout, Bn))
+    if tile is None:
+        tile = _tile(sig("fw", nin, nout, Bn), lambda: 1)
     rc = native.kernels().cxn_gemm_glds_sgd(A, Bo, nin, 1.0, w.data_ptr(), m.data_ptr(), wb.data_ptr(), float(lr),
                                             float(wd), float(mom), float(clip),
                                             hyp.data_ptr() if hyp is not None else None, tile, _stream())
-    if rc == -1:
-        return False
-    native.check(rc, "gemm_glds_sgd")
-    return True
+    return served(rc, "gemm_glds_sgd")
 
 
 def fc_backward_weight(x, dy, dw, overwrite=False):
@@ -1214,10 +1217,7 @@ def fc_backward_weight(x, dy, dw, overwrite=False):
     if _use("fw"):
         epi = EPI_F32 if overwrite else EPI_F32_ACC_G
         run = lambda t, o: _glds(A, Bo, GL_MN, GL_MN, o, 0, nin, epi=epi, tile=t)  # noqa: E731
-        if overwrite:
-            tile = _tuned_tile(("fw", nin, nout, Bn), run, dw, lambda: 1)
-        else:  # += epilogue: never time it on the live buffer
-            tile = _TUNE.get(f"fw|{nin}|{nout}|{Bn}", 1) if _glds_cfg["tile"] < 0 else _glds_cfg["tile"]
-        if run(tile, dw):
+        # the += epilogue is never timed on the live buffer: lookup only
+        if run(_tile(sig("fw", nin, nout, Bn), lambda: 1, run if overwrite else None, dw), dw):
             return
     _gemm(A, Bo, DIRECT_MN, DIRECT_MN, 8, 8, dw, 0, nin, epi=EPI_F32 if overwrite else EPI_F32_ACC)

@@ -51,3 +51,18 @@ def retire(t):
     """Keep a replaced workspace alive for the plans that may still reference it."""
     if t is not None:
         _GRAVE.append(t)
+
+
+_POOLS = {}
+
+
+def workspace(pool: str, n: int, device, min_size: int = 0):
+    """fp32 scratch of at least n elements (max(n, min_size) when it has to grow) from the named
+    per-device pool.  The pools only grow, and a replaced buffer is retired, not freed (see
+    above).  Pools stay separate by name: two of them can be live in the same step."""
+    bufs = _POOLS.setdefault(pool, {})
+    buf = bufs.get(str(device))
+    if buf is None or buf.numel() < n:
+        retire(buf)
+        buf = bufs[str(device)] = torch.empty(max(n, min_size), dtype=torch.float32, device=device)
+    return buf

@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import native
-from .mode import native as _native_t
+from .mode import native as _native_t, workspace
 from .gemm import _stream
 
 ACT_KIND = {"relu": 0, "sigmoid": 1, "tanh": 2, "xelu": 3}
@@ -558,20 +558,10 @@ def loss_grad(kind: str, node, label, scale: float, p32=None):
 
 
 # ----------------------------------------------------------------------------- reductions / misc
-_WS = {}
-
-
 def _workspace(n: int, device) -> torch.Tensor:
     """Reusable fp32 scratch (per device) for per-block partial sums; used in stream
     order on the compute stream only."""
-    key = str(device)
-    t = _WS.get(key)
-    if t is None or t.numel() < n:
-        from .mode import retire
-        retire(t)  # a recorded / captured step may still point at it
-        t = torch.empty(max(n, 1 << 16), dtype=torch.float32, device=device)
-        _WS[key] = t
-    return t
+    return workspace("partial_sums", n, device, 1 << 16)
 
 
 def bias_grad(dy2d, db, mask=None):

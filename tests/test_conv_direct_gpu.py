@@ -138,3 +138,52 @@ def test_direct_data_grad_deterministic():
         outs.append(dx)
     torch.cuda.synchronize()
     assert torch.equal(outs[0], outs[1])  # no atomics, fixed summation order
+
+
+@pytest.mark.parametrize("shape", [(3, 64, 64, 1), (2, 128, 128, 2)], ids=lambda c: "x".join(map(str, c)))
+@pytest.mark.parametrize("direction", ["cf", "cd"])
+def test_direct_table_tile_with_direct_kernel_off(direction, shape, monkeypatch):
+    """A table entry that names a direct pseudo-tile, with the direct kernel switched off: both
+    directions run the LDS-DMA GEMM on the heuristic tile with their normal epilogue -- the data
+    gradient with its bias-gradient epilogue -- exactly as with that tile forced.  (The smallest
+    shapes the direct kernel serves: odd N, and one grouped case.)"""
+    from cxxnet_amd import ops
+    N, C, Cout, groups = shape
+    g = ConvGeom(N, 13, 13, C, 13, 13, Cout, 3, 3, 1, 1, 1, groups)
+    monkeypatch.setitem(gemm._TUNE, gemm.sig(direction, N, 13, 13, C, Cout, 3, 3, 1, 1, 1, groups), 200)
+    monkeypatch.setattr(gemm, "_CD", "0")
+    w = _rnd((Cout, 3, 3, C // groups), 11, 0.05)
+    if direction == "cf":
+        x = _rnd((N, 13, 13, C), 12)
+        b = torch.randn(Cout, device=DEV) * 0.1
+        pick = gemm._pick_glds(Cout // groups, N * 169, groups)
+        ref = F.conv2d(_nchw(x), w.float().permute(0, 3, 1, 2), b, padding=1, groups=groups).clamp_min(0)
+
+        def call():
+            y = torch.full((N, 13, 13, Cout), 7.0, device=DEV, dtype=torch.bfloat16)
+            ops.conv_forward(x, w, b, y, g, relu=True)
+            return y, None
+    else:
+        dy = _rnd((N, 13, 13, Cout), 13)
+        act = torch.relu(_rnd((N, 13, 13, C), 14))  # relu(z) of the layer below
+        pick = gemm._pick_glds(C // groups, N * 169, groups)
+        ref = torch.nn.grad.conv2d_input((N, C, 13, 13), w.float().permute(0, 3, 1, 2), _nchw(dy), padding=1,
+                                         groups=groups) * (_nchw(act) > 0).float()
+
+        def call():
+            dx, db = act.clone(), torch.full((C,), 0.25, device=DEV)
+            assert ops.conv_backward_data(dy, w, dx, g, mask_relu=True, dbias=db) is True
+            return dx, db
+    gemm.LAST_GLDS[0] = None
+    out, db = call()
+    assert gemm.LAST_GLDS[0] == pick
+    gemm.set_glds(tile=pick)
+    try:
+        forced, _ = call()
+    finally:
+        gemm.set_glds(tile=-1)
+    torch.cuda.synchronize()
+    assert torch.equal(out, forced)  # same kernel, same epilogue
+    assert _err(out.permute(0, 3, 1, 2), ref) < 1e-2
+    if db is not None:
+        assert _err(db - 0.25, out.float().sum((0, 1, 2))) < 1e-3  # the column sums of the stored (bf16) dx

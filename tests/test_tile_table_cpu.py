@@ -68,9 +68,9 @@ def test_every_compiled_tile_is_used():
 
 
 def test_signature_keys_are_well_formed():
-    width = {"cf": 11, "cfs": 6, "cd": 11, "cw": 11, "cws": 11, "cr": 8, "cwr": 8, "fc": 5, "fw": 3, "fws": 3}
     for key in _table():
         parts = key.split("|")
-        assert parts[0] in width, key
-        assert len(parts) - 1 == width[parts[0]], key
+        assert parts[0] in G.SIG_FIELDS, key
+        assert len(parts) - 1 == len(G.SIG_FIELDS[parts[0]]), key
         assert all(p.lstrip("-").isdigit() for p in parts[1:]), key
+        assert G.sig(parts[0], *[int(p) for p in parts[1:]]) == key
