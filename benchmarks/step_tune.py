@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--ops", default="", help="only these op classes (comma list, e.g. fw)")
     ap.add_argument("--cands", default="", help="only these candidate tiles (comma list; the current entry is kept)")
     a = ap.parse_args()
+    from cxxnet_amd import native
     from cxxnet_amd.io.data import DataBatch
     from cxxnet_amd.models import load_conf
     from cxxnet_amd.nnet import NetTrainer
@@ -108,6 +109,8 @@ def main():
         if cur not in cands:
             cands.append(cur)
         times = {t: [] for t in cands}
+        # the streaming fc weight-gradient + SGD kernel ignores the tile: off while its tiles are timed
+        stream_was = native.kernels().cxn_gemm_set_sgd_stream(0) if op in ("fw", "fws") else None
         for _ in range(a.rounds):
             for t in cands:
                 G._TUNE[key] = t
@@ -118,6 +121,8 @@ def main():
                     print("skip", key, t, type(ex).__name__, flush=True)
                     G._TUNE[key] = cur
                     continue
+        if stream_was is not None:
+            native.kernels().cxn_gemm_set_sgd_stream(stream_was)
         ok = {t: statistics.median(v) for t, v in times.items() if v}
         best = min(ok, key=ok.get)
         new = best if ok[best] < ok[cur] * (1 - a.margin) else cur

@@ -37,6 +37,7 @@
 //   * epilogues staged per wave through LDS so every global access is a contiguous row
 //     segment: bf16 (+bias, relu, relu'-mask of the old value), fp32 split-K slab, fp32 +=,
 //     fp32 atomics.
+#include <atomic>
 #include <cstdlib>
 #include "gemm_glds_common.h"
 
@@ -682,6 +683,35 @@ CXN_API int cxn_gemm_glds_split(const CxnOperandG *a, const CxnOperandG *b, int 
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// The streaming form of the fused fc weight-grad + SGD step (fc_wgrad_sgd.hip): 0 = off (every call
+// takes the tile dispatch), 1 = on for the shapes it pays for (the default), 2 = on for every shape
+// it can serve (tests, probes).  CXXNET_FC_SGD_STREAM=0 starts with it off.  A served call does not
+// use its `tile` argument, so whatever decides between tiles of this op (table key "fws":
+// benchmarks/step_tune.py, benchmarks/fc_sgd_probe.py) switches the stream off while it times them.
+static int g_sgd_stream = [] {
+  const char *e = getenv("CXXNET_FC_SGD_STREAM");
+  const int v = e ? atoi(e) : 1;
+  return v < 0 ? 0 : v;
+}();
+static int g_sgd_stream_blocks = 0;  // > 0: the stream's block count (tests, probes); 0: what the CUs hold
+// calls the streaming kernel served (the tests check that there is no silent fall-through); atomic:
+// the data-parallel and side-stream paths call the entry point from their own threads
+static std::atomic<long> g_sgd_stream_calls{0};
+
+// Both return the previous setting.
+CXN_API int cxn_gemm_set_sgd_stream(int mode) {
+  const int old = g_sgd_stream;
+  g_sgd_stream = mode < 0 ? 0 : mode;
+  return old;
+}
+CXN_API int cxn_gemm_set_sgd_stream_blocks(int blocks) {
+  const int old = g_sgd_stream_blocks;
+  g_sgd_stream_blocks = blocks < 0 ? 0 : blocks;
+  return old;
+}
+
+CXN_API long cxn_gemm_sgd_stream_calls() { return g_sgd_stream_calls.load(std::memory_order_relaxed); }
+
 // fc weight-grad fused with the SGD step (single GPU, update_period 1): for every element of
 // dw = alpha * B^T A (MN-major x and dy, ldc = nin) the epilogue applies
 //   g = clip(dw); m = mom*m - lr*(g + wd*w); w += m; wb = bf16(w)
@@ -701,6 +731,10 @@ CXN_API int cxn_gemm_glds_sgd(const CxnOperandG *a, const CxnOperandG *b, int ld
   GEpi E{nullptr, 0, ldc, alpha, nullptr, 0, 0, 0, 0, w, m, static_cast<bf16_t *>(wb), lr, wd, mom, clip, nullptr, 0, 0, nullptr,
          g_gemm_group_i, hyp};
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (g_sgd_stream > 0 && cxg::dispatch_fc_sgd_stream(A, B, E, g_sgd_stream >= 2, g_sgd_stream_blocks, s) == 0) {
+    g_sgd_stream_calls.fetch_add(1, std::memory_order_relaxed);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+  }
   const int rc = dispatch(MN_DIRECT, MN_DIRECT, EPI_F32_SGD, tile, A, B, E, 1, 1, s);
   if (rc != 0) return rc;
   return hipGetLastError() == hipSuccess ? 0 : -3;

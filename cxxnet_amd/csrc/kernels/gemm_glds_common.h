@@ -598,5 +598,9 @@ int dispatch_halo(int amode, int bmode, int epi, int tile, GOperand A, GOperand 
 // direct 3x3 weight-gradient on resident halo / dy tiles (conv_wgrad_halo.hip): tiles 140-142
 int dispatch_wgrad_halo(int amode, int bmode, int epi, int tile, const GOperand &A, const GOperand &B, const GEpi &E,
                         int groups, hipStream_t s);
+// fc weight-gradient + SGD step as a parameter stream (fc_wgrad_sgd.hip); -1 when the shape is
+// not served
+int dispatch_fc_sgd_stream(const GOperand &A, const GOperand &B, const GEpi &E, bool forced, int blocks_set,
+                           hipStream_t s);
 
 }  // namespace cxg

@@ -70,6 +70,9 @@ _SIGS = {
     "cxn_gemm_glds_sgd": [ctypes.POINTER(CxnOperand), ctypes.POINTER(CxnOperand), _I, _F, _P, _P, _P, _F, _F, _F, _F,
                           _P, _I, _P],
     "cxn_gemm_set_group": [_I],
+    "cxn_gemm_set_sgd_stream": [_I],
+    "cxn_gemm_set_sgd_stream_blocks": [_I],
+    "cxn_gemm_sgd_stream_calls": [],
     "cxn_set_kernel_variant": [_I, _I],
     "cxn_gemm_glds_add": [ctypes.POINTER(CxnOperand), ctypes.POINTER(CxnOperand), _I, _I, _P, _L, _I, _P, _I, _I, _I,
                           _P],
@@ -144,7 +147,8 @@ _SIGS = {
     "cxn_conv_rowrun_fwd2": [_P, _P, _P, _P] + [_I] * 13 + [_P],
     "cxn_conv_direct": [_P, _I, _P, _P, _P, _I, _P, _L, _P] + [_I] * 10 + [_P],
 }
-_RESTYPE = {"cxn_rec_end": ctypes.c_void_p, "cxn_rec_free": None, "cxn_conv_wgrad_direct": ctypes.c_long,
+_RESTYPE = {"cxn_gemm_sgd_stream_calls": ctypes.c_long, "cxn_rec_end": ctypes.c_void_p, "cxn_rec_free": None,
+            "cxn_conv_wgrad_direct": ctypes.c_long,
             "cxn_conv_wgrad_rowrun": ctypes.c_long,
             "cxn_conv_direct": ctypes.c_long}
 
