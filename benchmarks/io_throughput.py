@@ -2,7 +2,7 @@
 JPEGs generated locally with Pillow (no dataset on the box).
 
   python benchmarks/io_throughput.py [--n 2048] [--size 256] [--workers 4,8,16] [--modes native,process,thread]
-                                     [--iters imgbin,imgbinx]
+                                     [--iters imgbin,imgbinx] [--affine] [--input 3,227,227]
 
 Writes N JPEG images (smooth random content, quality 90, ImageNet-like file sizes at the
 given side), packs them with im2bin into 64 MB pages, then times `iter = imgbin(x)` +
@@ -11,6 +11,12 @@ mean_value) at batch 256 for each worker count, decoding in the native C++ pool
 (decode_native), in the native pool's entropy stage + the GPU (gpu: decode_gpu, io/jpeg_stage.py),
 in Pillow processes (decode_process) or in Pillow threads (decode_thread).  Prints one JSON line per setting: img/s, img/s per busy host
 core, and the host cores one MI355X would need at its measured AlexNet training rate.
+
+--affine adds the affine keys of examples/kaggle_bowl/bowl.conf (rotation +-180, shear 0.3, aspect
+0.5) to every iterator config.  The modes then compare the two affine paths: `warp` is
+affine_gpu = 1 (native draws + source-region decode, the warp as a HIP kernel, io/warp_stage.py),
+every other mode is affine_gpu = 0, where any affine key sends the records through Pillow
+(`process` / `thread`).  --input sets input_shape (3,40,40 with --size 64 --batch 64 is the bowl).
 """
 import argparse
 import json
@@ -63,18 +69,26 @@ def make_trainer(model, batch):
     return tr
 
 
-def run(root, it_type, mode, workers, batches, batch, tr=None):
+AFFINE_KEYS = [("max_rotate_angle", "180"), ("max_aspect_ratio", "0.5"), ("max_shear_ratio", "0.3"),
+               ("min_crop_size", "32"), ("max_crop_size", "48")]  # examples/kaggle_bowl/bowl.conf
+
+
+def run(root, it_type, mode, workers, batches, batch, tr=None, affine=False, input_shape="3,227,227"):
     threads, procs = (workers, 0) if mode == "thread" else (1, workers)
-    nat = "1" if mode in ("native", "gpu") else "0"
+    nat = "1" if mode in ("native", "gpu", "warp") else "0"
+    on_gpu = mode in ("gpu", "warp")  # the batch is finished by a kernel: decode_gpu / affine_gpu
     from cxxnet_amd.io.iterators import create_iterator
     cfg = [("iter", it_type), ("image_list", os.path.join(root, "train.lst")),
            ("image_bin", os.path.join(root, "train.bin")), ("rand_crop", "1"), ("rand_mirror", "1"),
            ("mean_value", "104,117,123"), ("decode_thread", str(threads)), ("decode_process", str(procs)),
            ("decode_native", nat), ("decode_native_threads", str(workers)),
            ("decode_gpu", "1" if mode == "gpu" else "0"),
-           ("input_shape", "3,227,227"),
+           ("affine_gpu", "1" if mode == "warp" else "0"),
+           ("input_shape", input_shape)] + (AFFINE_KEYS if affine else []) + [
            ("batch_size", str(batch)), ("round_batch", "1"), ("silent", "1"), ("iter", "threadbuffer"),
            ("iter", "end")]
+    if tr is not None or on_gpu:
+        import torch
     it = create_iterator(cfg)
     it.init()
     it.before_first()
@@ -91,11 +105,12 @@ def run(root, it_type, mode, workers, batches, batch, tr=None):
         b = it.value()
         if tr is not None:
             tr.update(b)
+        elif mode == "warp":  # warp only, on the device the iterator prefetched to (as the trainer does)
+            b.data.to_u8(torch.device("cuda", torch.cuda.current_device()))
         elif mode == "gpu":  # decode only: finish the decode on the GPU
             b.data.to_u8("cuda")
         n += 1
-    if tr is not None or mode == "gpu":
-        import torch
+    if tr is not None or on_gpu:
         torch.cuda.synchronize()
     el = time.perf_counter() - t0
     it.close()
@@ -116,6 +131,9 @@ def main():
                     help="pack the list this many times (a multi-page .bin from few JPEGs: the page "
                          "reader's steady state)")
     ap.add_argument("--train", default="", help="also train this model (GPU) on the decoded batches")
+    ap.add_argument("--affine", action="store_true",
+                    help="add the bowl conf's affine keys; mode `warp` is affine_gpu = 1, the others affine_gpu = 0")
+    ap.add_argument("--input", default="3,227,227", help="input_shape")
     a = ap.parse_args()
     root = a.dir or tempfile.mkdtemp(prefix="cxxnet_io_")
     from cxxnet_amd.tools.im2bin import pack
@@ -137,10 +155,13 @@ def main():
     for it_type in a.iters.split(","):
         for mode in a.modes.split(","):
             for t in [int(v) for v in a.workers.split(",")]:
-                ips = run(root, it_type, mode, t, a.batches, a.batch, tr)
+                if mode == "warp" and not a.affine:
+                    raise SystemExit("mode warp needs --affine")
+                ips = run(root, it_type, mode, t, a.batches, a.batch, tr, a.affine, a.input)
                 per_core = ips / min(t, cores)
                 print(json.dumps({"iter": it_type, "mode": mode, "workers": t, "host_cpus": cores,
-                                  "train": a.train or None,
+                                  "train": a.train or None, "affine": a.affine, "input_shape": a.input,
+                                  "batch": a.batch,
                                   "img_per_s": round(ips, 1),
                                   "img_per_s_per_busy_core": round(per_core, 1), "jpeg_side": a.size,
                                   "avg_jpeg_bytes": int(avg),

@@ -46,6 +46,43 @@ static CropConfig ParseCropConfig(py::tuple cfg) {
   return c;
 }
 
+// (out_h, out_w, channels, rand_crop, rand_mirror, mirror, max_random_contrast,
+//  max_random_illumination, mean_mode, max_rotate_angle, max_shear_ratio, max_aspect_ratio,
+//  min_random_scale, max_random_scale, min_img_size, max_img_size, rotate, rotate_list, fill_value)
+static WarpConfig ParseWarpConfig(py::tuple cfg) {
+  if (cfg.size() != 19) throw std::runtime_error("JpegDecodePool: warp cfg has 19 fields");
+  WarpConfig c;
+  c.crop.out_h = cfg[0].cast<int>();
+  c.crop.out_w = cfg[1].cast<int>();
+  c.crop.channels = cfg[2].cast<int>();
+  c.crop.rand_crop = cfg[3].cast<int>();
+  c.crop.rand_mirror = cfg[4].cast<int>();
+  c.crop.mirror = cfg[5].cast<int>();
+  c.crop.max_random_contrast = cfg[6].cast<float>();
+  c.crop.max_random_illumination = cfg[7].cast<float>();
+  c.crop.mean_mode = cfg[8].cast<int>();
+  c.max_rotate_angle = cfg[9].cast<int>();
+  c.max_shear_ratio = cfg[10].cast<double>();
+  c.max_aspect_ratio = cfg[11].cast<double>();
+  c.min_random_scale = cfg[12].cast<double>();
+  c.max_random_scale = cfg[13].cast<double>();
+  c.min_img_size = cfg[14].cast<double>();
+  c.max_img_size = cfg[15].cast<double>();
+  c.rotate = cfg[16].cast<int>();
+  c.rotate_list = cfg[17].cast<std::vector<int>>();
+  c.fill_value = cfg[18].cast<int>();
+  if (c.crop.channels < 1 || c.crop.channels > 3) throw std::runtime_error("JpegDecodePool: 1-3 channels");
+  if (c.crop.out_h < 1 || c.crop.out_w < 1) throw std::runtime_error("JpegDecodePool: empty warp output");
+  if (c.fill_value < 0 || c.fill_value > 255) throw std::runtime_error("JpegDecodePool: fill_value is a byte");
+  return c;
+}
+
+static long CheckWarpTable(py::array_t<int64_t> &table) {
+  if (table.ndim() != 2 || table.shape(1) != kWarpTable || !(table.flags() & py::array::c_style))
+    throw std::runtime_error("JpegDecodePool: table must be a C-contiguous [B][16] int64 array");
+  return table.shape(0);
+}
+
 static void CheckPrmCm(py::array_t<int32_t> &prm, py::array_t<float> &cm, long B) {
   if (prm.ndim() != 2 || prm.shape(0) != B || prm.shape(1) != 4 || cm.ndim() != 2 || cm.shape(0) != B ||
       cm.shape(1) != 2 || !(prm.flags() & py::array::c_style) || !(cm.flags() & py::array::c_style))
@@ -322,7 +359,72 @@ PYBIND11_MODULE(_cxxnet_rt, m) {
           },
           "Entropy-decode every (row, payload, seed) into the GPU decode stage (coef blocks, their window "
           "ids, per-row window tables; ops.jpeg_decode finishes on the GPU); returns (rows left to "
-          "decode(), blocks used)");
+          "decode(), blocks used)")
+      .def(
+          "plan_warp",
+          [](JpegDecodePool &pool, py::list items, py::tuple cfg, py::array_t<int64_t> table,
+             py::array_t<double> draws, py::array_t<int32_t> prm, py::array_t<float> cm) {
+            WarpConfig c = ParseWarpConfig(cfg);
+            const long B = CheckWarpTable(table);
+            if (draws.ndim() != 2 || draws.shape(0) != B || draws.shape(1) != kWarpDraws ||
+                !(draws.flags() & py::array::c_style))
+              throw std::runtime_error("JpegDecodePool.plan_warp: draws must be a C-contiguous [B][8] float64 array");
+            CheckPrmCm(prm, cm, B);
+            std::vector<py::buffer_info> keep;
+            std::vector<DecodeItem> its = ParseItems(items, B, keep);
+            int64_t *tp = table.mutable_data();
+            double *dp = draws.mutable_data();
+            int32_t *pp = prm.mutable_data();
+            float *cp = cm.mutable_data();
+            std::pair<std::vector<int>, std::vector<int>> r;
+            {
+              py::gil_scoped_release rel;
+              r = pool.RunPlanWarp(its, c, tp, dp, pp, cp);
+            }
+            return py::make_tuple(r.first, r.second);
+          },
+          "Warp stage, phase 1: header, augmentation draws, output->source map and source region of every "
+          "(row, payload, seed) into its table row (runtime/jpeg_decode.h WarpTableField); returns (rows to "
+          "decode with Pillow, rows whose warped image is smaller than the crop)")
+      .def(
+          "decode_regions",
+          [](JpegDecodePool &pool, py::list items, py::array_t<int64_t> table, py::array_t<uint8_t> buf) {
+            const long B = CheckWarpTable(table);
+            if (buf.ndim() != 1 || !(buf.flags() & py::array::c_style))
+              throw std::runtime_error("JpegDecodePool.decode_regions: buf must be a contiguous uint8 array");
+            std::vector<py::buffer_info> keep;
+            std::vector<DecodeItem> its = ParseItems(items, B, keep);
+            const int64_t *tp = table.data();
+            const int64_t nbuf = buf.shape(0);
+            for (const DecodeItem &it : its) {
+              const int64_t *t = tp + static_cast<long>(it.row) * kWarpTable;
+              if (t[kWValid] == 0) continue;
+              if (t[kWRw] < 0 || t[kWRh] < 0 || t[kWRw] > 65536 || t[kWRh] > 65536 || t[kWOffset] < 0 ||
+                  t[kWOffset] + t[kWRw] * t[kWRh] * 3 > nbuf)
+                throw std::runtime_error("JpegDecodePool.decode_regions: region outside the packed buffer");
+            }
+            uint8_t *bp = buf.mutable_data();
+            std::vector<int> failed;
+            {
+              py::gil_scoped_release rel;
+              failed = pool.RunRegions(its, tp, bp);
+            }
+            return failed;
+          },
+          "Warp stage, phase 2: decode every valid row's source region to packed RGB at its table offset; "
+          "returns the rows that failed to decode")
+      .def_static(
+          "draw_warp",
+          [](uint64_t seed, int W, int H, py::tuple cfg) -> py::object {
+            WarpConfig c = ParseWarpConfig(cfg);
+            WarpDraw d;
+            if (!DrawWarp(H, W, c, seed, &d)) return py::none();
+            std::vector<double> draws(d.draws, d.draws + kWarpDraws), m(d.m, d.m + 6);
+            return py::make_tuple(draws, m, py::make_tuple(d.x0, d.y0, d.rw, d.rh), d.mirror, d.contrast, d.illum);
+          },
+          "The warp draws of one seed for a W x H image (what plan_warp writes for a JPEG of that size): "
+          "(draws, m0..m5, (x0, y0, rw, rh), mirrored, contrast, illumination), or None when the warped "
+          "image is smaller than the crop");
 
   py::class_<ImageListEntry>(m, "ImageListEntry")
       .def_readonly("index", &ImageListEntry::index)

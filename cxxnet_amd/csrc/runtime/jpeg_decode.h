@@ -17,12 +17,15 @@
 //     generator seeded by the per-record seed the iterator draws, so a batch does not depend
 //     on the thread count or on which thread decoded which record;
 //   * a record libjpeg cannot decode to RGB (PNG, CMYK JPEG, corrupt data) is reported back
-//     and decoded by the Pillow path instead.
+//     and decoded by the Pillow path instead;
+//   * with affine augmentation on the GPU (affine_gpu = 1) the pool draws each record's warp and
+//     decodes the source region it touches (DrawWarp / PlanWarp / DecodeRegion below).
 #pragma once
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <csetjmp>
 #include <cstdint>
@@ -520,6 +523,229 @@ inline int ReadCoefCrop(const jpg::Api &J, const unsigned char *buf, size_t len,
   return 0;
 }
 
+// ---- GPU affine warp stage: draws + source-region decode here, the warp itself on the GPU -----
+//
+// With affine_gpu = 1 (io/warp_stage.py) the random rotate / shear / scale / aspect warp of
+// io/augment.py _affine (reference src/io/image_augmenter-inl.hpp:74-121) runs as a HIP kernel
+// (csrc/kernels/warp_kernels.hip).  The host draws every record's augmentation, builds the
+// output-pixel -> source-position map, and decodes only the part of the image that map can
+// touch into one packed RGB buffer.
+//
+// Per-image table: kWarpTable 8-byte words per batch row (int64, the map as float64 bit
+// patterns).  The one definition of the layout; io/warp_stage.py and warp_kernels.hip mirror it.
+constexpr int kWarpTable = 16;
+enum WarpTableField {
+  kWValid = 0,   // 1: warped from the packed buffer; 0: padding / another rank's row (zeros)
+  kWOffset = 1,  // byte offset of the region in the packed buffer (rw * rh * 3 bytes, RGB)
+  kWX0 = 2,      // region origin in the image
+  kWY0 = 3,
+  kWRw = 4,      // region size (0 x 0: the whole output is fill)
+  kWRh = 5,
+  kWImgW = 6,    // image size: a tap outside [0, W) x [0, H) contributes the fill value
+  kWImgH = 7,
+  kWM0 = 8,      // m0..m5 (float64): sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5
+  kWFill = 14,
+};
+// Raw draws returned beside the table (float64 per row) so the map can be recomputed.
+constexpr int kWarpDraws = 8;
+enum WarpDrawField { kDShear = 0, kDAngle = 1, kDScale = 2, kDRatio = 3, kDCropY = 4, kDCropX = 5, kDMirror = 6 };
+
+// The affine subset of AugmentParam (io/augment.py) plus the crop settings the warp path uses.
+struct WarpConfig {
+  CropConfig crop;
+  int max_rotate_angle = 0, rotate = -1, fill_value = 255;
+  double max_shear_ratio = 0, max_aspect_ratio = 0, min_random_scale = 1, max_random_scale = 1;
+  double min_img_size = 0, max_img_size = 1e10;
+  std::vector<int> rotate_list;
+};
+
+struct WarpDraw {
+  double draws[kWarpDraws];
+  double m[6];
+  int x0, y0, rw, rh;
+  bool mirror;
+  float contrast, illum;
+};
+
+// One record's draws for a W x H image, from its own generator: the order of io/augment.py
+// _affine (shear, angle, scale, aspect ratio, crop offset within new_w x new_h), then DrawCrop's
+// contrast, illumination, mirror.  Builds _affine's forward matrix in double, inverts it and folds
+// in the crop offset and the mirror (x -> w - 1 - x).  False when the warped image is smaller than
+// the crop (new_w < w or new_h < h).
+inline bool DrawWarp(int H, int W, const WarpConfig &c, uint64_t seed, WarpDraw *d) {
+  using namespace jpg;
+  const double kPi = 3.14159265358979323846;
+  const int ch = c.crop.out_h, cw = c.crop.out_w;
+  Rng rng(seed);
+  const double s = rng.uniform() * c.max_shear_ratio * 2 - c.max_shear_ratio;
+  int angle = 0;
+  if (c.max_rotate_angle > 0)
+    angle = static_cast<int>(rng.below(static_cast<uint32_t>(c.max_rotate_angle) * 2)) - c.max_rotate_angle;
+  if (c.rotate > 0) angle = c.rotate;
+  if (!c.rotate_list.empty()) {
+    // the reference samples NextUInt32(size - 1): the last entry is never drawn
+    const size_t n = c.rotate_list.size();
+    angle = c.rotate_list[n > 1 ? rng.below(static_cast<uint32_t>(n - 1)) : 0];
+  }
+  const double a = std::cos(angle / 180.0 * kPi), b = std::sin(angle / 180.0 * kPi);
+  const double scale = rng.uniform() * (c.max_random_scale - c.min_random_scale) + c.min_random_scale;
+  const double ratio = rng.uniform() * c.max_aspect_ratio * 2 - c.max_aspect_ratio + 1;
+  const double hs = 2 * scale / (1 + ratio), ws = ratio * hs;
+  const int new_w = static_cast<int>(std::max(c.min_img_size, std::min(c.max_img_size, scale * W)));
+  const int new_h = static_cast<int>(std::max(c.min_img_size, std::min(c.max_img_size, scale * H)));
+  const double m00 = hs * a - s * b * ws, m01 = hs * b + s * a * ws, m10 = -b * ws, m11 = a * ws;
+  const double m02 = (new_w - (m00 * W + m01 * H)) / 2, m12 = (new_h - (m10 * W + m11 * H)) / 2;
+  const double det = m00 * m11 - m01 * m10;
+  const double i00 = m11 / det, i01 = -m01 / det, i10 = -m10 / det, i11 = m00 / det;
+  const double i02 = -(i00 * m02 + i01 * m12), i12 = -(i10 * m02 + i11 * m12);
+  int yy = new_h - ch, xx = new_w - cw;
+  if (yy < 0 || xx < 0) return false;
+  if (c.crop.rand_crop) {
+    yy = static_cast<int>(rng.below(static_cast<uint32_t>(yy + 1)));
+    xx = static_cast<int>(rng.below(static_cast<uint32_t>(xx + 1)));
+  } else {
+    yy /= 2;
+    xx /= 2;
+  }
+  float contrast =
+      static_cast<float>(rng.uniform() * c.crop.max_random_contrast * 2 - c.crop.max_random_contrast + 1);
+  float illum =
+      static_cast<float>(rng.uniform() * c.crop.max_random_illumination * 2 - c.crop.max_random_illumination);
+  bool mirror;
+  if (c.crop.mean_mode == 0) {
+    mirror = c.crop.rand_mirror && rng.uniform() < 0.5;
+    contrast = 1.f;
+    illum = 0.f;
+  } else {
+    mirror = (c.crop.rand_mirror && rng.uniform() < 0.5) || c.crop.mirror == 1;
+  }
+  // output pixel (x, y) is pixel (xo + xx, y + yy) of the warped image, xo = mirror ? cw - 1 - x : x
+  const double sgn = mirror ? -1.0 : 1.0, xb = mirror ? cw - 1 + xx : xx;
+  d->m[0] = sgn * i00, d->m[1] = i01, d->m[2] = i00 * xb + i01 * yy + i02;
+  d->m[3] = sgn * i10, d->m[4] = i11, d->m[5] = i10 * xb + i11 * yy + i12;
+  // source region: bounding box of the four output corners, 3 pixels wider, clamped to the image
+  double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+  for (int k = 0; k < 4; ++k) {
+    const double x = (k & 1) ? cw - 1 : 0, y = (k & 2) ? ch - 1 : 0;
+    const double p[2] = {d->m[0] * x + d->m[1] * y + d->m[2], d->m[3] * x + d->m[4] * y + d->m[5]};
+    for (int j = 0; j < 2; ++j) lo[j] = std::min(lo[j], p[j]), hi[j] = std::max(hi[j], p[j]);
+  }
+  const int dim[2] = {W, H};
+  int r0[2], r1[2];
+  for (int j = 0; j < 2; ++j) {
+    const double l = std::max(std::floor(lo[j]) - 3, 0.0), h = std::min(std::ceil(hi[j]) + 3, dim[j] - 1.0);
+    r0[j] = static_cast<int>(l);
+    r1[j] = h >= l ? static_cast<int>(h) + 1 : r0[j];  // exclusive; empty when the box misses the image
+  }
+  if (r1[0] == r0[0] || r1[1] == r0[1]) r0[0] = r0[1] = r1[0] = r1[1] = 0;
+  d->x0 = r0[0], d->y0 = r0[1], d->rw = r1[0] - r0[0], d->rh = r1[1] - r0[1];
+  d->draws[kDShear] = s, d->draws[kDAngle] = angle, d->draws[kDScale] = scale, d->draws[kDRatio] = ratio;
+  d->draws[kDCropY] = yy, d->draws[kDCropX] = xx, d->draws[kDMirror] = mirror ? 1 : 0, d->draws[7] = 0;
+  d->mirror = mirror, d->contrast = contrast, d->illum = illum;
+  return true;
+}
+
+inline void WriteWarpRow(const WarpDraw &d, int W, int H, int fill, int64_t *t, double *draws) {
+  t[kWValid] = 1, t[kWOffset] = 0, t[kWX0] = d.x0, t[kWY0] = d.y0, t[kWRw] = d.rw, t[kWRh] = d.rh;
+  t[kWImgW] = W, t[kWImgH] = H, t[kWFill] = fill, t[kWFill + 1] = 0;
+  std::memcpy(t + kWM0, d.m, sizeof(d.m));
+  std::memcpy(draws, d.draws, sizeof(d.draws));
+}
+
+// Reads one record's header and plans its warp into table row t.  Returns 0, -1 (not a record
+// libjpeg decodes to RGB: 12-bit, CMYK -> the Pillow decode), -2 (warped image smaller than the
+// crop), or a libjpeg message code.
+inline int PlanWarp(const jpg::Api &J, const unsigned char *buf, size_t len, const WarpConfig &c, uint64_t seed,
+                    int64_t *t, double *draws, int *prm, float *cm) {
+  using namespace jpg;
+  jpeg_decompress_struct cinfo;
+  ErrMgr err;
+  std::memset(&cinfo, 0, sizeof(cinfo));
+  cinfo.err = J.std_error(&err.pub);
+  err.pub.error_exit = on_error;
+  err.pub.emit_message = on_message;
+  err.code = 0;
+  volatile bool created = false;
+  if (setjmp(err.jb)) {
+    if (created) J.destroy_decompress(&cinfo);
+    return err.code > 0 ? err.code : -1;
+  }
+  J.create_decompress(&cinfo, JPEG_LIB_VERSION, sizeof(cinfo));
+  created = true;
+  J.mem_src(&cinfo, buf, static_cast<unsigned long>(len));
+  J.read_header(&cinfo, 1);
+  const int H = static_cast<int>(cinfo.image_height), W = static_cast<int>(cinfo.image_width);
+  const int cs = cinfo.jpeg_color_space;
+  const bool ok = cinfo.data_precision == 8 && (cs == JCS_GRAYSCALE || cs == JCS_RGB || cs == JCS_YCbCr);
+  J.destroy_decompress(&cinfo);
+  if (!ok) return -1;
+  WarpDraw d;
+  if (!DrawWarp(H, W, c, seed, &d)) return -2;
+  WriteWarpRow(d, W, H, c.fill_value, t, draws);
+  prm[0] = 0, prm[1] = 0, prm[2] = d.mirror ? 1 : 0, prm[3] = 0;
+  cm[0] = d.contrast, cm[1] = d.illum;
+  return 0;
+}
+
+// Decodes rows y0..y0+rh, columns x0..x0+rw of one record to packed RGB at out (rw * 3 bytes per
+// row): rows above are skipped, rows below never decoded, columns narrowed with the margins of
+// DecodeCrop (bit-identical to a full decode).  Returns 0, or -1 / a libjpeg message code.
+inline int DecodeRegion(const jpg::Api &J, const unsigned char *buf, size_t len, const int64_t *t, unsigned char *out,
+                        std::vector<unsigned char> &row) {
+  using namespace jpg;
+  const int x0 = static_cast<int>(t[kWX0]), y0 = static_cast<int>(t[kWY0]), rw = static_cast<int>(t[kWRw]),
+            rh = static_cast<int>(t[kWRh]);
+  if (rw <= 0 || rh <= 0) return 0;
+  jpeg_decompress_struct cinfo;
+  ErrMgr err;
+  std::memset(&cinfo, 0, sizeof(cinfo));
+  cinfo.err = J.std_error(&err.pub);
+  err.pub.error_exit = on_error;
+  err.pub.emit_message = on_message;
+  err.code = 0;
+  volatile bool created = false;
+  if (setjmp(err.jb)) {
+    if (created) J.destroy_decompress(&cinfo);
+    return err.code > 0 ? err.code : -1;
+  }
+  J.create_decompress(&cinfo, JPEG_LIB_VERSION, sizeof(cinfo));
+  created = true;
+  J.mem_src(&cinfo, buf, static_cast<unsigned long>(len));
+  J.read_header(&cinfo, 1);
+  cinfo.out_color_space = JCS_RGB;
+  cinfo.dct_method = JDCT_ISLOW;
+  const int H = static_cast<int>(cinfo.image_height), W = static_cast<int>(cinfo.image_width);
+  if (W != t[kWImgW] || H != t[kWImgH] || x0 < 0 || y0 < 0 || x0 + rw > W || y0 + rh > H) {
+    J.destroy_decompress(&cinfo);
+    return -1;
+  }
+  J.start_decompress(&cinfo);
+  if (cinfo.output_components != 3) {
+    J.abort_decompress(&cinfo);
+    J.destroy_decompress(&cinfo);
+    return -1;
+  }
+  JDIMENSION xa = static_cast<JDIMENSION>(x0 > 0 ? x0 - 1 : 0);
+  JDIMENSION wd = static_cast<JDIMENSION>(std::min(x0 + rw + 16, W)) - xa;
+  J.crop_scanline(&cinfo, &xa, &wd);  // xa <= x0, xa + wd >= x0 + rw
+  const int dx = x0 - static_cast<int>(xa);
+  row.resize(static_cast<size_t>(cinfo.output_width) * 3 + 64);
+  if (y0 > 0) J.skip_scanlines(&cinfo, static_cast<JDIMENSION>(y0));
+  for (int y = 0; y < rh; ++y) {
+    JSAMPROW rp = row.data();
+    if (J.read_scanlines(&cinfo, &rp, 1) != 1) {
+      J.abort_decompress(&cinfo);
+      J.destroy_decompress(&cinfo);
+      return -1;
+    }
+    std::memcpy(out + static_cast<size_t>(y) * rw * 3, row.data() + static_cast<size_t>(dx) * 3,
+                static_cast<size_t>(rw) * 3);
+  }
+  J.abort_decompress(&cinfo);
+  J.destroy_decompress(&cinfo);
+  return 0;
+}
+
 // Persistent decode thread pool.  Run() hands a batch of records to every thread and
 // returns when all are done (the caller's thread works too).
 class JpegDecodePool {
@@ -616,7 +842,74 @@ class JpegDecodePool {
     return {failed, std::min(st.cursor.load(), st.cap_blocks)};
   }
 
+  // Warp stage, phase 1: every record's header, draws and source region into its table row
+  // (PlanWarp).  Returns (rows libjpeg cannot decode to RGB, rows whose warped image is smaller
+  // than the crop); both keep valid = 0.
+  std::pair<std::vector<int>, std::vector<int>> RunPlanWarp(const std::vector<DecodeItem> &items,
+                                                            const WarpConfig &cfg, int64_t *table, double *draws,
+                                                            int32_t *prm, float *cm) {
+    const jpg::Api &J = jpg::api();
+    if (!J.ok) throw std::runtime_error("native JPEG decoder unavailable: " + J.error);
+    std::vector<int> status(items.size(), 0);
+    auto work = [&](size_t i, std::vector<unsigned char> &, std::string &filebuf) {
+      const DecodeItem &it = items[i];
+      const unsigned char *p;
+      size_t n;
+      if (!LoadItem(it, filebuf, &p, &n)) {
+        status[i] = -1;
+        return;
+      }
+      const int r = it.row;
+      status[i] = PlanWarp(J, p, n, cfg, it.seed, table + static_cast<long>(r) * kWarpTable,
+                           draws + static_cast<long>(r) * kWarpDraws, prm + 4 * r, cm + 2 * r);
+      if (status[i] != 0) table[static_cast<long>(r) * kWarpTable + kWValid] = 0;
+    };
+    Dispatch(items.size(), work);
+    std::pair<std::vector<int>, std::vector<int>> out;
+    for (size_t i = 0; i < items.size(); ++i)
+      if (status[i] != 0) (status[i] == -2 ? out.second : out.first).push_back(items[i].row);
+    return out;
+  }
+
+  // Warp stage, phase 2: decode each valid row's region to buf + its table offset (the caller
+  // checked that every region lies inside buf).  Returns the rows that failed to decode.
+  std::vector<int> RunRegions(const std::vector<DecodeItem> &items, const int64_t *table, unsigned char *buf) {
+    const jpg::Api &J = jpg::api();
+    if (!J.ok) throw std::runtime_error("native JPEG decoder unavailable: " + J.error);
+    std::vector<int> failed_flag(items.size(), 0);
+    auto work = [&](size_t i, std::vector<unsigned char> &rowbuf, std::string &filebuf) {
+      const DecodeItem &it = items[i];
+      const int64_t *t = table + static_cast<long>(it.row) * kWarpTable;
+      if (t[kWValid] == 0 || t[kWRw] * t[kWRh] == 0) return;
+      const unsigned char *p;
+      size_t n;
+      if (!LoadItem(it, filebuf, &p, &n) || DecodeRegion(J, p, n, t, buf + t[kWOffset], rowbuf) != 0)
+        failed_flag[i] = 1;
+    };
+    Dispatch(items.size(), work);
+    std::vector<int> failed;
+    for (size_t i = 0; i < items.size(); ++i)
+      if (failed_flag[i]) failed.push_back(items[i].row);
+    return failed;
+  }
+
  private:
+  // the record's encoded bytes (read from its path into filebuf when it has none); false when
+  // the file cannot be read or is not a JPEG (PNG, ...)
+  static bool LoadItem(const DecodeItem &it, std::string &filebuf, const unsigned char **pp, size_t *pn) {
+    const unsigned char *p = it.data;
+    size_t n = it.size;
+    if (p == nullptr) {
+      std::ifstream f(it.path, std::ios::binary);
+      if (!f) return false;
+      filebuf.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+      p = reinterpret_cast<const unsigned char *>(filebuf.data());
+      n = filebuf.size();
+    }
+    *pp = p, *pn = n;
+    return n >= 4 && p[0] == 0xFF && p[1] == 0xD8;
+  }
+
   void Dispatch(size_t n, std::function<void(size_t, std::vector<unsigned char> &, std::string &)> work) {
     {
       std::lock_guard<std::mutex> lk(mu_);

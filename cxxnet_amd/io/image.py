@@ -23,7 +23,9 @@ MI355X-first design:
     reference's decode thread (iter_thread_imbin_x-inl.hpp:150-388, utils/decoder.h).
     Affine augmentation and non-JPEG records take the Pillow path: worker processes
     writing into a shared batch buffer (io/augment.py; a thread pool when
-    decode_process = 0).
+    decode_process = 0).  With affine_gpu = 1 the affine warp runs on the GPU instead
+    (io/warp_stage.py): the native pool draws each record's warp and decodes the source
+    region it touches, one HIP kernel warps the batch.
   * A batch leaves the host as uint8 (``U8Images``).  Mean subtraction, contrast,
     illumination, scale and the NHWC-bf16 conversion happen on the GPU in one fused
     kernel (``ops.image_to_nhwc``).  That is 4x less PCIe traffic than fp32 and
@@ -33,7 +35,8 @@ MI355X-first design:
 
 Decoding uses Pillow (OpenCV is not available here).  Pixels are RGB like the
 reference's BGR->RGB conversion.  The affine warp uses Pillow's bicubic resampler,
-so warped pixels are not bit-identical to OpenCV's INTER_CUBIC (parity unpinned).
+so warped pixels are not bit-identical to OpenCV's INTER_CUBIC (parity unpinned); with
+affine_gpu = 1 it follows OpenCV's published fixed-point scheme (io/warp_stage.py).
 """
 from __future__ import annotations
 
@@ -46,10 +49,11 @@ import numpy as np
 import torch
 
 from .. import native
-from .augment import AugmentParam, DecodePool, ShmBuffer, _augment_one, default_decode_process, default_native_threads, shm_available
-from . import jpeg_stage
+from .augment import AugmentParam, DecodePool, ShmBuffer, _augment_one, _decode, default_decode_process, default_native_threads, shm_available
+from . import jpeg_stage, warp_stage
 from .data import DEVICE_IO_LOCK, DataBatch, DataIterator, U8Images, input_device
 from .jpeg_stage import JpegCoefImages
+from .warp_stage import WarpImages
 
 
 # ----------------------------------------------------------------------------- records
@@ -291,7 +295,13 @@ class ImageBatchIterator(DataIterator):
     least 4, else 0: the Pillow path decodes in that many worker processes, io/augment.py,
     writing into a shared-memory batch; 0 = use threads), decode_thread (threads when
     decode_process is 0; default min(8, cpus)), shard_decode (default 1: under
-    torch.distributed each rank decodes only its own rows of the batch).  Results do not
+    torch.distributed each rank decodes only its own rows of the batch), affine_gpu (default 0;
+    1: with affine augmentation active and the native pool available, the pool draws each
+    record's warp and decodes only the source region it touches, and the warp itself runs as a
+    HIP kernel in the step's input stage, io/warp_stage.py -- bicubic with OpenCV's fixed-point
+    scheme, not Pillow's resampler; like the native crop path its draws come from the native
+    generator, not the Pillow path's: a seed picks different draws from the same
+    distribution).  Results do not
     depend on the worker counts: every record's augmentation draws are seeded from the
     iterator's stream (the native and Pillow paths draw crops from different generators, so
     switching decode_native changes which crops a seed picks, not their distribution)."""
@@ -315,6 +325,8 @@ class ImageBatchIterator(DataIterator):
         self.decode_native = 1
         self.decode_native_threads = 0
         self.decode_gpu = -1
+        self.affine_gpu = 0
+        self._warp = False
         self.prefetch_device = -1
         self.dev = None  # the trainer's `dev` (global conf key): the device the batches feed
         self._dev: Optional[torch.device] = None
@@ -353,6 +365,8 @@ class ImageBatchIterator(DataIterator):
             self.decode_native_threads = int(val)
         elif name == "decode_gpu":
             self.decode_gpu = int(val)
+        elif name == "affine_gpu":
+            self.affine_gpu = int(val)
         elif name == "prefetch_device":
             self.prefetch_device = int(val)
         elif name == "dev":
@@ -373,7 +387,8 @@ class ImageBatchIterator(DataIterator):
         elif self._dev is None:
             self.prefetch_device = 0  # nothing on a GPU consumes the batches
         C, h, w = self.aug.shape
-        if self.decode_native and h > 1 and C <= 3 and not self.aug.need_affine():
+        self._warp = bool(self.affine_gpu) and self.aug.need_affine()
+        if self.decode_native and h > 1 and C <= 3 and (self._warp or not self.aug.need_affine()):
             rt = native.rt()
             if rt.JpegDecodePool.available():
                 n = self.decode_native_threads or default_native_threads()
@@ -382,6 +397,7 @@ class ImageBatchIterator(DataIterator):
                     self.decode_gpu = int(self._dev is not None)
             elif not self.silent:
                 print(f"native JPEG decoder unavailable ({rt.JpegDecodePool.error()}): decoding with Pillow")
+        self._warp = self._warp and self._jpeg is not None
         if self.aug.mean_value is not None and any(v > 0 for v in self.aug.mean_value):
             # the reference subtracts mean_value[i] from channel i (iter_augment_proc-inl.hpp:64-67,128)
             self.mean = torch.tensor(self.aug.mean_value, dtype=torch.float32)
@@ -505,6 +521,11 @@ class ImageBatchIterator(DataIterator):
         prm, cm = prm_t.numpy(), cm_t.numpy()
         prm.fill(0)
         cm[:, 0], cm[:, 1] = 1.0, 0.0
+        if self._warp:
+            data = self._stage_warp(rows, seeds, B)
+            if self.prefetch_device:
+                data.prefetch(self._dev)
+            return DataBatch(data, label, index, padd)
         if self._jpeg is not None and self.decode_gpu > 0:
             data = self._stage_jpeg(rows, seeds, (B, h, w, C))
             if self.prefetch_device:
@@ -584,6 +605,17 @@ class ImageBatchIterator(DataIterator):
                                       lambda payload, seed: _augment_one(payload, self.aug, seed, self.mean_mode))
         return JpegCoefImages(coef, bwin, meta, nblk, prm, cm, (h, w, C), fb, failed, self.mean, self.mean_mode,
                               self.aug.scale)
+
+    def _stage_warp(self, rows, seeds, B) -> WarpImages:
+        """affine_gpu: the native pool draws each row's warp and decodes the source region it touches
+        into one packed pinned buffer; the warp runs where the batch is consumed (io/warp_stage.py).
+        Records the native decoder does not take are decoded in full by Pillow into the same buffer."""
+        C, h, w = self.aug.shape
+        cfg = warp_stage.warp_cfg(self.aug, self.mean_mode)
+        items = [(i, r.payload, seeds[i]) for i, r in rows]
+        src, table, prm, cm, _, _ = warp_stage.stage_batch(self._jpeg, items, cfg, B, torch.cuda.is_available(),
+                                                           _decode)
+        return WarpImages(src, table, prm, cm, (h, w, C), self.mean, self.mean_mode, self.aug.scale)
 
     def _decode_procs(self, rows, seeds, shape, prm, cm) -> torch.Tensor:
         nbytes = int(np.prod(shape))

@@ -106,6 +106,7 @@ _SIGS = {
     "cxn_zero_ranges": [_P, _P, _P, _I, _P],
     "cxn_jpeg_idct": [_P, _P, _P, _L, _P, _P],
     "cxn_jpeg_color": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "cxn_image_warp": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "cxn_nhwc_bf16_to_nchw_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "cxn_transpose": [_P, _P, _I, _I, _I, _P],
     "cxn_conv_weight_flip": [_P, _P, _I, _I, _I, _I, _I, _P],

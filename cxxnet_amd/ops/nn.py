@@ -6,6 +6,7 @@ All activations are NHWC (see ops/gemm.py for the layout contract).
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 
 import torch
@@ -80,21 +81,57 @@ def jpeg_decode(coef, bwin, meta, nblk: int, prm, r0: int, r1: int, h: int, w: i
 _CONST = {}
 
 
-def _device_const(t: torch.Tensor, dev) -> torch.Tensor:
-    """fp32 device copy of a host tensor that does not change between batches (the iterator's
-    mean), made once: a pageable copy per step would stall the host on the stream."""
+def _device_const(t: torch.Tensor, dev, dtype=torch.float32) -> torch.Tensor:
+    """Device copy (fp32 unless told otherwise) of a host tensor that does not change between
+    batches (the iterator's mean, the warp's weight table), made once: a pageable copy per step
+    would stall the host on the stream."""
     key = (id(t), str(dev))
     hit = _CONST.get(key)
     if hit is None or hit[0] is not t:
-        hit = _CONST[key] = (t, t.to(dev, torch.float32).contiguous())
+        hit = _CONST[key] = (t, t.to(dev, dtype).contiguous())
     return hit[1]
+
+
+@functools.lru_cache(maxsize=None)
+def _warp_weights() -> torch.Tensor:
+    from ..io import warp_stage
+    return torch.from_numpy(warp_stage.cubic_table().copy())
+
+
+def image_warp(src, table, r0: int, r1: int, h: int, w: int, C: int, dev, staged=None) -> torch.Tensor:
+    """GPU half of the affine warp stage (io/warp_stage.py): packed RGB source regions + the
+    per-image table -> uint8 (r1 - r0, h, w, C) warped crops of rows r0..r1 on `dev` (bicubic,
+    constant border, bit-equal to warp_stage.warp_reference; csrc/kernels/warp_kernels.hip).
+    staged: device copies of (src, table) already made (io/data.py DevicePrefetch)."""
+    from ..io import warp_stage
+    B = int(table.shape[0])
+    if not (0 <= r0 <= r1 <= B) or tuple(table.shape[1:]) != (warp_stage.TABLE,) or table.dtype != torch.int64 or \
+            src.dtype != torch.uint8 or src.dim() != 1 or not 1 <= C <= 3 or h < 1 or w < 1:
+        raise ValueError("image_warp: inconsistent stage")
+    if max(h, w) > warp_stage.MAX_SIDE:
+        raise ValueError("image_warp: output larger than 16384 px a side")
+    # host-side bounds of what the kernel will index (numpy, like jpeg_decode)
+    warp_stage.check_table(table.numpy()[r0:r1], int(src.shape[0]), h, w)
+    out = torch.empty((r1 - r0, h, w, C), dtype=torch.uint8, device=dev)
+    if r1 == r0:
+        return out
+    if staged is not None:
+        src_d, table_d = staged
+    else:
+        src_d = src.to(dev, non_blocking=True)
+        table_d = table.to(dev, non_blocking=True)
+    wtab = _device_const(_warp_weights(), dev, torch.int32)  # built once per device
+    native.check(_k().cxn_image_warp(src_d.data_ptr(), table_d.data_ptr(), wtab.data_ptr(), r0, r1, h, w, C,
+                                     out.data_ptr(), _stream()), "image_warp")
+    return out
 
 
 def image_to_nhwc(img, out: torch.Tensor):
     """U8Images batch -> NHWC input node with the augmenter arithmetic fused
     (GPU: one kernel over uint8 pixels; CPU: the fp32 reference)."""
     from ..io.jpeg_stage import JpegCoefImages
-    if isinstance(img, JpegCoefImages):  # finish the JPEG decode where the batch is going
+    from ..io.warp_stage import WarpImages
+    if isinstance(img, (JpegCoefImages, WarpImages)):  # finish the decode / warp where the batch is going
         img = img.to_u8(out.device if _native_t(out) else None)
     if not _native_t(out):
         input_to_nhwc(img.to_float(), out)
