@@ -2,11 +2,17 @@
 torch: forward (bias + relu epilogue) and the stride-1 data-gradient (plain and relu'-masked),
 one and several 64-channel blocks (single and double-buffered halo), 32- and 16-pixel-wide
 patches, patches cut by the map's right and bottom edges, output channels not a multiple of the
-block.  Each case asserts that the forced tile really ran (gemm.LAST_GLDS)."""
+block.  Each case asserts that the forced tile really ran (gemm.LAST_GLDS), and, beside the
+whole-tensor norm, every element against a float64 reference under the derived bound of
+tests/bounds.py (a cut patch edge or one channel block gone wrong moves the norm by less than
+bf16 rounding does)."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
+import bounds
 from cxxnet_amd import ops
 from cxxnet_amd.ops import gemm
 from cxxnet_amd.ops.gemm import ConvGeom
@@ -39,13 +45,39 @@ def _geom(N, H, W, C, Cout):
     return ConvGeom(N, H, W, C, H, W, Cout, 3, 3, 1, 1, 1, 1)
 
 
+# operands and float64 references per (case, seeds): the tile / mask parameters share them
+@functools.lru_cache(maxsize=4)
+def _fwd_case(case, seed):
+    g = _geom(*case)
+    x = _rnd((g.N, g.H, g.W, g.C), 1.0, seed)
+    w = _rnd((g.Cout, 3, 3, g.C), 0.05, seed + 1)
+    b = torch.randn(g.Cout, generator=torch.Generator(device=DEV).manual_seed(seed + 2), device=DEV) * 0.1
+    return x, w, b, bounds.forward_ref(x, w, b, pad=1, relu=True)
+
+
+@functools.lru_cache(maxsize=4)
+def _dgrad_case(case, seed):
+    g = _geom(*case)
+    dy = _rnd((g.N, g.H, g.W, g.Cout), 1.0, seed)
+    w = _rnd((g.Cout, 3, 3, g.C), 0.05, seed + 1)
+    z = _rnd((g.N, g.H, g.W, g.C), 1.0, seed + 2)  # relu(z) in dx on entry when masked
+    return dy, w, z, bounds.data_grad_ref(dy, w, pad=1)
+
+
+def _check_dgrad(dx, z, refs, mask, what):
+    ref64, bound = refs
+    if mask:
+        m = z.cpu() > 0
+        assert torch.count_nonzero(dx.cpu()[~m]) == 0, what + ": a masked element is not 0"
+        ref64, bound = ref64 * m, bound * m
+    print(what, "max d/bound %.3f" % bounds.assert_within(dx, ref64, bound, what))
+
+
 @pytest.mark.parametrize("tile", TILES)
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
 def test_halo_forward(tile, case):
     g = _geom(*case)
-    x = _rnd((g.N, g.H, g.W, g.C), 1.0, 1)
-    w = _rnd((g.Cout, 3, 3, g.C), 0.05, 2)
-    b = torch.randn(g.Cout, device=DEV) * 0.1
+    x, w, b, (ref64, bound) = _fwd_case(case, 1)
     y = torch.full((g.N, g.H, g.W, g.Cout), 9.0, dtype=torch.bfloat16, device=DEV)
     gemm.set_glds(tile=tile)
     gemm.LAST_GLDS[0] = None
@@ -56,6 +88,8 @@ def test_halo_forward(tile, case):
     assert gemm.LAST_GLDS[0] == tile
     ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b, padding=1)
     assert _rel(y, ref.clamp_min(0).permute(0, 2, 3, 1)) < 1e-2
+    what = "halo forward %s tile %d" % (case, tile)
+    print(what, "max d/bound %.3f" % bounds.assert_within(y, ref64, bound, what))
 
 
 # (the data-gradient gathers dy: its Cout is the blocked channel count, C the output rows)
@@ -67,9 +101,7 @@ DGRAD = [(2, 16, 64, 64, 64), (2, 20, 48, 128, 128), (1, 9, 40, 64, 192), (3, 8,
 @pytest.mark.parametrize("case", DGRAD, ids=lambda c: "x".join(map(str, c)))
 def test_halo_data_grad(tile, mask, case):
     g = _geom(*case)
-    dy = _rnd((g.N, g.H, g.W, g.Cout), 1.0, 3)
-    w = _rnd((g.Cout, 3, 3, g.C), 0.05, 4)
-    z = _rnd((g.N, g.H, g.W, g.C), 1.0, 5)  # relu(z) in dx on entry when masked
+    dy, w, z, refs = _dgrad_case(case, 3)
     dx = z.clamp_min(0) if mask else torch.empty_like(z)
     gemm.set_glds(tile=tile)
     gemm.LAST_GLDS[0] = None
@@ -83,6 +115,7 @@ def test_halo_data_grad(tile, mask, case):
     if mask:
         ref = ref * (z.float() > 0)
     assert _rel(dx, ref) < 1e-2
+    _check_dgrad(dx, z, refs, mask, "halo data gradient %s tile %d mask %d" % (case, tile, mask))
 
 
 def test_halo_declines_other_convs():
@@ -124,9 +157,7 @@ def test_halo_persistent_forward(tile, case):
     if Cout > PS_TILES[tile]:
         pytest.skip("more output channels than the persistent block")
     g = _geom(N, H, W, C, Cout)
-    x = _rnd((N, H, W, C), 1.0, 11)
-    w = _rnd((Cout, 3, 3, C), 0.05, 12)
-    b = torch.randn(Cout, device=DEV) * 0.1
+    x, w, b, (ref64, bound) = _fwd_case(case, 11)
     y = torch.full((N, H, W, Cout), 9.0, dtype=torch.bfloat16, device=DEV)
     gemm.set_glds(tile=tile)
     gemm.LAST_GLDS[0] = None
@@ -137,6 +168,8 @@ def test_halo_persistent_forward(tile, case):
     assert gemm.LAST_GLDS[0] == tile
     ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b, padding=1)
     assert _rel(y, ref.clamp_min(0).permute(0, 2, 3, 1)) < 1e-2
+    what = "halo persistent forward %s tile %d" % (case, tile)
+    print(what, "max d/bound %.3f" % bounds.assert_within(y, ref64, bound, what))
 
 
 @pytest.mark.parametrize("tile", sorted(PS_TILES))
@@ -145,9 +178,7 @@ def test_halo_persistent_forward(tile, case):
 def test_halo_persistent_data_grad(tile, mask, cin):
     N, H, W = 6, 24, 64  # dy cin channels (the blocked operand) -> dx 64 channels
     g = _geom(N, H, W, 64, cin)
-    dy = _rnd((N, H, W, cin), 1.0, 13)
-    w = _rnd((cin, 3, 3, 64), 0.05, 14)
-    z = _rnd((N, H, W, 64), 1.0, 15)
+    dy, w, z, refs = _dgrad_case((N, H, W, 64, cin), 13)
     dx = z.clamp_min(0) if mask else torch.empty_like(z)
     gemm.set_glds(tile=tile)
     gemm.LAST_GLDS[0] = None
@@ -161,6 +192,7 @@ def test_halo_persistent_data_grad(tile, mask, cin):
     if mask:
         ref = ref * (z.float() > 0)
     assert _rel(dx, ref) < 1e-2
+    _check_dgrad(dx, z, refs, mask, "halo persistent data gradient cin %d tile %d mask %d" % (cin, tile, mask))
 
 
 def test_halo_persistent_declines_two_output_blocks():
@@ -188,9 +220,7 @@ def test_halo_data_grad_bias_sum(tile, mask, case):
     """EPI_BF16_DB on the halo tiles: dx exactly as the plain epilogue writes it, and dbias += the
     column sums of the stored (relu'-masked) dx, from per-(patch, wave) partial rows."""
     g = _geom(*case)
-    dy = _rnd((g.N, g.H, g.W, g.Cout), 1.0, 21)
-    w = _rnd((g.Cout, 3, 3, g.C), 0.05, 22)
-    z = _rnd((g.N, g.H, g.W, g.C), 1.0, 23)
+    dy, w, z, refs = _dgrad_case(case, 21)
     gemm.set_glds(tile=tile)
     try:
         dx_ref = z.clamp_min(0) if mask else torch.empty_like(z)
@@ -206,3 +236,7 @@ def test_halo_data_grad_bias_sum(tile, mask, case):
     assert torch.equal(dx, dx_ref)
     ref = 0.25 + dx_ref.float().reshape(-1, g.C).sum(0)
     assert _rel(db, ref) < 1e-3
+    what = "halo data gradient + bias sum %s tile %d mask %d" % (case, tile, mask)
+    _check_dgrad(dx, z, refs, mask, what)
+    dref, dbound = bounds.dbias_ref(dx, 0.25)
+    print(what, "dbias max d/bound %.3g" % bounds.assert_within(db, dref, dbound, what + " dbias", axes="c"))

@@ -4,10 +4,14 @@ pad 3, 64 outputs -- padding staged on the fly) against fp32 torch.  Weight grad
 the 8-GPU strong-scaling batch, odd image counts, a map whose last row group is short (14 output
 rows = 3 groups of 4 + 2), a channel-sliced dy, accumulation into dw, bitwise repeatability and
 the shapes it must refuse.  Forward: the same batches and maps, bias / relu, an output channel
-slice of a wider buffer (nothing outside it written), and the conv_forward dispatch."""
+slice of a wider buffer (nothing outside it written), and the conv_forward dispatch; up to
+N = 32 the forward is also checked element by element against a float64 reference under the
+derived bound of tests/bounds.py."""
 import torch.nn.functional as F
 import pytest
 import torch
+
+import bounds
 
 from cxxnet_amd.ops import gemm
 from cxxnet_amd.ops.gemm import ConvGeom
@@ -101,6 +105,9 @@ def test_rowrun_fwd2(N, H, ldc, relu, bias):
         ref = ref.clamp_min(0)
     got = y.float().permute(0, 3, 1, 2)
     assert ((got - ref).norm() / ref.norm()).item() < 5e-3
+    if N <= 32:
+        ref64, bound = bounds.forward_ref(x, w, b, stride=4, relu=relu)
+        print("rowrun forward N %d H %d: max d/bound %.3f" % (N, H, bounds.assert_within(y, ref64, bound, "rowrun forward")))
     if ldc > 96:
         assert torch.all(yb[..., 96:] == 7.0)  # nothing outside the slice
 
@@ -153,3 +160,7 @@ def test_rowrun_googlenet_fwd(N, H, relu):
     if relu:
         ref = ref.clamp_min(0)
     assert ((y.float().permute(0, 3, 1, 2) - ref).norm() / ref.norm()).item() < 5e-3
+    if N <= 32:
+        ref64, bound = bounds.forward_ref(x, w, b, stride=2, pad=3, relu=relu)
+        print("rowrun forward (7 x 7 / 2) N %d H %d: max d/bound %.3f" % (
+            N, H, bounds.assert_within(y, ref64, bound, "rowrun forward 7 x 7 / 2")))

@@ -2,10 +2,18 @@
 tiles 140-142) against fp32 torch: both patch widths, ragged maps (partial patches and row
 bands), a pre-padded input (pad 0 geometry on an (H+2) x (W+2) map, as the prepadding conv
 layers pass it), a dy channel slice (pixel stride > Cout), several channel pairs and splits.
-Each case asserts that the forced tile really ran (gemm.LAST_GLDS)."""
+Each case asserts that the forced tile really ran (gemm.LAST_GLDS).  Cases with N H W up to
+about 1500 are also checked element by element, dw itself (onto a random dw0), against a float64
+reference under the derived fp32 bound of tests/bounds.py: the output is fp32 accumulated in
+fp32 (MFMA partial sums, one atomic per split), so a 1e-2 norm leaves room for several wholly
+wrong elements; beyond that K the bound grows past one missing pixel term and the norm stays
+the only check."""
+import functools
+
 import pytest
 import torch
 
+import bounds
 from cxxnet_amd import ops
 from cxxnet_amd.ops import gemm
 from cxxnet_amd.ops.gemm import ConvGeom
@@ -21,7 +29,13 @@ CASES = [
     (1, 13, 13, 256, 128, 141),  # AlexNet-like 13 x 13, 8 channel pairs
     (2, 20, 37, 64, 64, 141),    # ragged in both directions
     (2, 20, 37, 64, 64, 142),
+    (1, 13, 13, 64, 64, 140),    # one small case per tile and patch shape: one partial patch,
+    (2, 20, 37, 64, 64, 140),
+    (3, 14, 14, 64, 128, 141),
+    (1, 13, 13, 64, 64, 142),    # a map narrower than the 32-wide patch
+    (3, 14, 14, 64, 128, 142),
 ]
+BOUND_K = 1600  # N H W up to which the elementwise fp32 bound is applied (tests/bounds.py)
 
 
 def _rnd(shape, seed):
@@ -35,9 +49,18 @@ def _ref(x, dy, pad):
                                        stride=1, padding=pad)
 
 
-def _run(x, dy, g, tile):
+@functools.lru_cache(maxsize=None)
+def _bound_case(shape):
+    """operands, a random dw0 and the float64 reference / bound of dw0 + the weight gradient"""
+    N, H, W, C, Cout = shape
+    x, dy = _rnd((N, H, W, C), 1), _rnd((N, H, W, Cout), 2)
+    dw0 = torch.randn(Cout, 3, 3, C, generator=torch.Generator(device=DEV).manual_seed(3), device=DEV)
+    return x, dy, dw0, bounds.weight_grad_ref(x, dy, dw0, pad=1)
+
+
+def _run(x, dy, g, tile, dw0=None):
     Cout, C = g.Cout, g.C
-    dw = torch.full((Cout, 3, 3, C), 0.5, device=DEV)
+    dw = torch.full((Cout, 3, 3, C), 0.5, device=DEV) if dw0 is None else dw0.clone()
     gemm.set_glds(tile=tile)
     gemm.LAST_GLDS[0] = None
     try:
@@ -46,6 +69,8 @@ def _run(x, dy, g, tile):
         gemm.set_glds(tile=-1)
     torch.cuda.synchronize()
     assert gemm.LAST_GLDS[0] == tile
+    if dw0 is not None:
+        return dw
     return (dw - 0.5).permute(0, 3, 1, 2)
 
 
@@ -61,6 +86,11 @@ def test_wgrad_halo(case):
     dy = _rnd((N, H, W, Cout), 2)
     err = _err(_run(x, dy, g, tile), _ref(x, dy, 1))
     assert err < 1e-2, err
+    if N * H * W <= BOUND_K:
+        x, dy, dw0, (ref64, bound) = _bound_case(case[:5])
+        what = "wgrad halo %s" % (case,)
+        worst = bounds.assert_within(_run(x, dy, g, tile, dw0), ref64, bound, what, axes=("co", "kh", "kw", "ci"))
+        print(what, "max d/bound %.3g" % worst)
 
 
 def test_wgrad_halo_prepadded_and_dy_slice():
