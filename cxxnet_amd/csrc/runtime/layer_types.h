@@ -39,6 +39,8 @@ enum : int {
   kPRelu = 29,
   kBatchNorm = 30,
   kFixConnect = 31,
+  // extensions without a reference counterpart: ids the reference enumeration leaves unused
+  kBatchNormMA = 40,
   kPairTestGap = 1024,
 };
 
@@ -57,6 +59,7 @@ inline int GetLayerType(const std::string &t) {
       {"insanity", kInsanity}, {"insanity_max_pooling", kInsanityPooling},
       {"l2_loss", kL2Loss}, {"multi_logistic", kMultiLogistic},
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
+      {"batch_norm_ma", kBatchNormMA},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,8 +1,9 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
-insanity, insanity_max_pooling, fixconn, pairtest.
+insanity, insanity_max_pooling, fixconn, pairtest -- and the extension batch_norm_ma.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
-insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), concat / split /
+insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
+csrc/kernels/bn_ma_kernels.hip, concat / split /
 bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
@@ -252,6 +253,106 @@ class BatchNormLayer(Layer):
 
     def load_model(self, fi: BinReader):
         self.loaded = [fi.read_tensor(1), fi.read_tensor(1)]
+
+    def loaded_values(self):
+        return self.loaded
+
+
+class BatchNormMALayer(Layer):
+    """`batch_norm_ma` (type id 40) -- an extension, no reference counterpart: batch
+    normalisation that trains on the batch statistics, keeps a moving average of them
+    (running <- bn_momentum running + (1 - bn_momentum) batch, biased variance, from 0 / 1) and
+    normalises with that average when is_train is False, so a row's inference output does not
+    depend on its batch neighbours.  Unlike `batch_norm` the input node is not overwritten with
+    x-hat and no copy of x is kept (backward reads x from the input node and overwrites it with
+    dx) unless the layer is a self-loop.  slope ("wmat") and bias ("bias") are arena parameters;
+    the running statistics are state, views [mean | var] into the net's flat bn_state buffer
+    (NeuralNet._build_bn_state), never seen by the optimizer.  The checkpoint holds slope, bias,
+    running_mean, running_var."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "batch_norm_ma"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.init_slope = 1.0
+        self.init_bias = 0.0
+        self.eps = 1e-5
+        self.momentum = 0.9
+        self.rmean = self.rvar = None
+        self._st = None
+        self.loaded = None
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "init_slope":
+            self.init_slope = float(val)
+        elif name == "init_bias":
+            self.init_bias = float(val)
+        elif name == "eps":
+            self.eps = float(val)
+        elif name == "bn_momentum":
+            self.momentum = float(val)
+            _check(0.0 <= self.momentum < 1.0, "BatchNormMALayer: bn_momentum must be in [0, 1)")
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "BatchNormMALayer: only support 1-1 connection")
+        nodes_out[0].set_shape(*nodes_in[0].shape, cp=nodes_in[0].cp)
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "BatchNormMALayer: padded-channel input is not supported")
+        self.channel = _num_feat(nodes_in[0])
+        b, c, h, w = nodes_in[0].shape
+        self.max_rows = b * c * h * w // self.channel
+        self.self_loop = nodes_in[0] is nodes_out[0]
+        self.params = [ParamSpec("wmat", (self.channel,), _bias_init(self.init_slope)),
+                       ParamSpec("bias", (self.channel,), _bias_init(self.init_bias))]
+
+    # ---- running statistics (NeuralNet._build_bn_state)
+    def state_numel(self):
+        return 2 * self.channel
+
+    def bind_state(self, buf):
+        """buf: this layer's [mean | var] slice of net.bn_state."""
+        self.rmean, self.rvar = buf[:self.channel], buf[self.channel:]
+        self.rmean.zero_()
+        self.rvar.fill_(1.0)
+
+    def load_state(self, vals):
+        """vals: loaded_values() of a layer of this type; the two tensors after the parameters."""
+        if len(vals) >= 4:
+            self.rmean.copy_(vals[2].reshape(-1))
+            self.rvar.copy_(vals[3].reshape(-1))
+
+    def _view(self, t):
+        return t.view(-1, self.channel)
+
+    def _state(self, x):
+        if self._st is None:
+            self._st = L.BNMAState(self.channel, self.max_rows, x.device, x.dtype, self.self_loop)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = self._view(nodes_in[0].data)
+        if is_train:
+            self.ctx.bn_dirty = True  # data parallel: rank 0's statistics go out before the next read
+        L.bn_ma_forward(x, self._view(nodes_out[0].data), self.params[0].w, self.params[1].w, self.eps, self.momentum,
+                        self._state(x), self.rmean, self.rvar, is_train)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        g = self._view(nodes_out[0].data)
+        st = self._state(g)
+        x = st.xsave[:g.shape[0]] if self.self_loop else self._view(nodes_in[0].data)
+        L.bn_ma_backward(g, x, self._view(nodes_in[0].gdst), self.params[0].w, self.params[0].g, self.params[1].g,
+                         st, prop_grad)
+
+    def save_model(self, fo: BinWriter):
+        fo.write_tensor(self.params[0].w)
+        fo.write_tensor(self.params[1].w)
+        fo.write_tensor(self.rmean)
+        fo.write_tensor(self.rvar)
+
+    def load_model(self, fi: BinReader):
+        self.loaded = [fi.read_tensor(1) for _ in range(4)]
 
     def loaded_values(self):
         return self.loaded
@@ -566,6 +667,7 @@ def _register():
     register(18, lambda ctx: ConcatLayer(ctx, 3))
     register(28, lambda ctx: ConcatLayer(ctx, 1))
     register(30, BatchNormLayer)
+    register(40, BatchNormMALayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -90,6 +90,11 @@ _SIGS = {
     "cxn_bn_stats": [_P, _P, _P, _P, _L, _I, _F, _P],
     "cxn_bn_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
     "cxn_bn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
+    # batch_norm_ma (csrc/kernels/bn_ma_kernels.hip)
+    "cxn_bn_ma_ws_floats": [_L, _I],
+    "cxn_bn_ma_fwd_train": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _F, _F, _P],
+    "cxn_bn_ma_fwd_infer": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "cxn_bn_ma_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "cxn_rand_fill": [_P, _L, _U, _I, _F, _F, _P],
     "cxn_prelu": [_P, _P, _P, _P, _L, _I, _U, _P, _F, _I, _P],
     "cxn_insanity": [_P, _P, _P, _P, _L, _F, _F, _I, _U, _P, _I, _P],
@@ -149,7 +154,7 @@ _SIGS = {
     "cxn_conv_direct": [_P, _I, _P, _P, _P, _I, _P, _L, _P] + [_I] * 10 + [_P],
 }
 _RESTYPE = {"cxn_gemm_sgd_stream_calls": ctypes.c_long, "cxn_rec_end": ctypes.c_void_p, "cxn_rec_free": None,
-            "cxn_conv_wgrad_direct": ctypes.c_long,
+            "cxn_conv_wgrad_direct": ctypes.c_long, "cxn_bn_ma_ws_floats": ctypes.c_long,
             "cxn_conv_wgrad_rowrun": ctypes.c_long,
             "cxn_conv_direct": ctypes.c_long}
 

@@ -615,6 +615,37 @@ class NeuralNet:
         self.arena.build(specs, groups=getattr(self, "sib_groups", ()))
         self._sibling_views()
 
+    def _state_layers(self):
+        """Layers that carry non-parameter state (batch_norm_ma), in connection order.  Inside a
+        pairtest such a layer is rejected: the pair's joined blob (PairTestLayer.loaded_values)
+        has no place for the state of its two sides."""
+        out = []
+        for conn in self.connections:
+            if conn.shared:
+                continue
+            lay = conn.layer
+            if any(hasattr(side, "bind_state") for side in (getattr(lay, "master", None), getattr(lay, "slave", None))):
+                raise ValueError("pairtest does not support batch_norm_ma (a layer with running statistics)")
+            if hasattr(lay, "bind_state"):
+                out.append(lay)
+        return out
+
+    def _build_bn_state(self):
+        """Running statistics of every batch_norm_ma layer in ONE flat fp32 buffer (each layer
+        holds views [mean | var] into it), so that reset, broadcast and snapshot are one operation
+        each.  Not part of the arena: the optimizer, weight decay and the gradient buckets never
+        see it.  None for a net without such a layer."""
+        self.bn_state = None
+        self.ctx.bn_dirty = False
+        lays = self._state_layers()
+        if not lays:
+            return
+        self.bn_state = torch.zeros(sum(l.state_numel() for l in lays), dtype=torch.float32, device=self.device)
+        off = 0
+        for l in lays:
+            l.bind_state(self.bn_state[off:off + l.state_numel()])
+            off += l.state_numel()
+
     def _init_updater(self):
         self.updater = ArenaUpdater(self.cfg.updater_type, self.arena, self.arena.segments(), self.cfg.defcfg,
                                     self.cfg.layercfg)
@@ -626,6 +657,7 @@ class NeuralNet:
         self._fuse()
         self._alloc_nodes()
         self._build_arena()
+        self._build_bn_state()
         # drawn in reverse layer order, each layer's tensors in declaration order -- not in arena
         # order, which sibling groups (ParamArena.build groups) rearrange: a seed gives the same
         # initial weights with and without the groups
@@ -651,12 +683,15 @@ class NeuralNet:
         self._fuse()
         self._alloc_nodes()
         self._build_arena()
+        self._build_bn_state()
         for conn in self.connections:
             if conn.shared or not hasattr(conn.layer, "loaded_values"):
                 continue
             vals = conn.layer.loaded_values()
             for spec, v in zip(conn.layer.params, vals):
                 spec.w.copy_(v.reshape(spec.shape))
+            if hasattr(conn.layer, "load_state"):  # tensors after the parameters: running statistics
+                conn.layer.load_state(vals)
         self.arena.sync_shadow()
         self._init_updater()
 

@@ -298,6 +298,35 @@ class NetTrainer:
             net = self.net
             self.reducer.enable_overlapped_update(lambda ranges: net.update(self.epoch_counter, ranges))
         self.reducer.broadcast_params()
+        self._snapshot_bn_state()
+
+    def _snapshot_bn_state(self, collective: bool = True):
+        """Keep the running statistics a fresh start goes back to (reset_to).  collective: every
+        rank is here (as for broadcast_params), and all of them start from rank 0's."""
+        net = self.net
+        if net.bn_state is None:
+            return
+        if collective:
+            net.ctx.bn_dirty = True
+            self._sync_bn_state()
+        self._bn_state0 = net.bn_state.clone()
+
+    def _sync_bn_state(self):
+        """Data parallelism: each rank moves its batch_norm_ma running statistics with its own
+        slice of the batch; rank 0's are authoritative (it always holds rows).  Before anything
+        reads them -- a save, an evaluation, a forward-only task -- they are broadcast from rank
+        0, if a training forward ran since the last broadcast.  Training forwards run in lockstep,
+        so the flag agrees on every rank and all of them enter the collective.  No collective at
+        world 1, no call at all in a net without the layer."""
+        net = self.net
+        if net is None or net.bn_state is None or not net.ctx.bn_dirty:
+            return
+        net.ctx.bn_dirty = False
+        if self.world > 1 and _dist_ready():
+            import torch.distributed as dist
+            if self.reducer is not None:
+                self.reducer.sync()
+            dist.broadcast(net.bn_state, src=0)
 
     def init_model(self):
         self.net_cfg.configure(self.cfg)
@@ -310,6 +339,7 @@ class NetTrainer:
         """Collective part of a save: every rank calls it (sharded mode gathers the fp32
         masters and, with opt_state, the optimizer state), then rank 0 serialises with
         save_model(sync=False) / save_optimizer_state(sync=False)."""
+        self._sync_bn_state()
         if self.reducer is not None:
             self.reducer.sync_master(opt_state=opt_state)
 
@@ -363,10 +393,13 @@ class NetTrainer:
                 if v.numel() != spec.numel:
                     raise ValueError(f"CopyModelFrom: layer {name} shape mismatch")
                 spec.w.copy_(v.reshape(spec.shape))
+            if hasattr(dst, "load_state"):  # running statistics travel with the layer
+                dst.load_state(vals)
             print(f"Copying layer {name}")
         self.net.arena.sync_shadow()
         if self.reducer is not None:
             self.reducer.broadcast_params()
+        self._snapshot_bn_state()
 
     def copy_model_from(self, other: "NetTrainer"):
         """Finetune: copy every layer whose name matches (reference nnet_impl-inl.hpp:101-134)."""
@@ -384,7 +417,10 @@ class NetTrainer:
             print(f"Copying layer {name}")
             for a, b in zip(sl.params, dl.params):
                 b.w.copy_(a.w.to(b.w.device))
+            if hasattr(dl, "load_state") and hasattr(sl, "load_state"):
+                dl.load_state([None, None, sl.rmean, sl.rvar])
         self.net.arena.sync_shadow()
+        self._snapshot_bn_state(collective=False)  # (no collective here: parameters are not broadcast either)
 
     # ------------------------------------------------------------------ training
     def reset_to(self, w0: torch.Tensor):
@@ -402,6 +438,9 @@ class NetTrainer:
         a.reset_state()
         a.sync_shadow()
         self.net.ctx.step_counter.zero_()
+        if self.net.bn_state is not None:  # in place: the layers hold views, plans hold addresses
+            self.net.bn_state.copy_(self._bn_state0)
+            self.net.ctx.bn_dirty = False
         self.epoch_counter = self.sample_counter = 0
         self._nf_flag = None
         self.train_metric.clear()
@@ -453,6 +492,8 @@ class NetTrainer:
             self.net.updater.fused_offsets.clear()
         self._set_batch(batch, local)
         net = self.net
+        if net.bn_state is not None:  # (a replayed plan does not run the layers' Python forward)
+            net.ctx.bn_dirty = True
         self._cur_batch = batch
         ev = self._events()
         if self.net.ctx.is_gpu:
@@ -1044,6 +1085,7 @@ class NetTrainer:
         return out
 
     def forward_to(self, node_ids: List[int], batch) -> List[np.ndarray]:
+        self._sync_bn_state()
         self.reducer.sync()
         self._set_batch(batch)
         self.net.forward(False)
@@ -1073,6 +1115,7 @@ class NetTrainer:
         return self.forward_to([nid], batch)[0]
 
     def evaluate(self, it, data_name: str) -> str:
+        self._sync_bn_state()
         ret = ""
         if self.eval_train != 0:
             if self.device_metrics:

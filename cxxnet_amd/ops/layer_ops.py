@@ -131,6 +131,79 @@ def bn_backward(g2d, dx2d, slope, gslope, gbias, st: BNState, prop_grad: bool):
                                  st.ws.data_ptr(), st.coef.data_ptr(), rows, C, _stream()), "bn_bwd")
 
 
+# ----------------------------------------------------------------------------- batch norm (running statistics)
+class BNMAState:
+    """Per-layer device buffers of batch_norm_ma, sized once for max_rows: stat [5][C] =
+    mean | var | inv | a | b of the last forward, the backward coefficients, the partial
+    workspace of the fixed-order reductions (csrc/kernels/bn_ma_kernels.hip), and -- self-loop
+    only -- the saved input."""
+
+    def __init__(self, C, max_rows, device, dtype, keep_x):
+        self.stat = torch.zeros(5, C, dtype=torch.float32, device=device)
+        self.coef = torch.zeros(3, C, dtype=torch.float32, device=device)
+        self.ws = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_bn_ma_ws_floats(int(max_rows), int(C)))
+            self.ws = torch.zeros(max(n, 1), dtype=torch.float32, device=device)
+        self.xsave = torch.zeros(max_rows, C, dtype=dtype, device=device) if keep_x else None
+
+
+def bn_ma_forward(x2d, y2d, slope, bias, eps, momentum, st: BNMAState, rmean, rvar, is_train: bool):
+    """Training: normalise with the batch's mean and biased variance and move the running
+    statistics towards them (running <- m running + (1 - m) batch).  Inference: normalise with
+    the running statistics alone.  y may alias x when st.xsave keeps the input (self-loop)."""
+    rows, C = x2d.shape
+    xsave = st.xsave[:rows] if (st.xsave is not None and is_train) else None
+    if not _native_t(x2d):
+        x = x2d.float()
+        if is_train:
+            mean = x.mean(0)
+            var = ((x - mean) ** 2).mean(0)
+            rmean.copy_(momentum * rmean + (1.0 - momentum) * mean)
+            rvar.copy_(momentum * rvar + (1.0 - momentum) * var)
+            if xsave is not None:
+                xsave.copy_(x2d)
+        else:
+            mean, var = rmean, rvar
+        inv = 1.0 / torch.sqrt(var + eps)
+        if is_train:
+            st.stat[0].copy_(mean)
+            st.stat[1].copy_(var)
+            st.stat[2].copy_(inv)
+        y2d.copy_((x - mean) * inv * slope + bias)
+        return
+    k = _k()
+    if is_train:
+        native.check(k.cxn_bn_ma_fwd_train(x2d.data_ptr(), y2d.data_ptr(), xsave.data_ptr() if xsave is not None else None,
+                                           slope.data_ptr(), bias.data_ptr(), st.stat.data_ptr(), rmean.data_ptr(),
+                                           rvar.data_ptr(), st.ws.data_ptr(), st.ws.numel(), rows, C, float(eps),
+                                           float(momentum), _stream()), "bn_ma_fwd_train")
+    else:
+        native.check(k.cxn_bn_ma_fwd_infer(x2d.data_ptr(), y2d.data_ptr(), slope.data_ptr(), bias.data_ptr(),
+                                           rmean.data_ptr(), rvar.data_ptr(), st.stat.data_ptr(), rows, C, float(eps),
+                                           _stream()), "bn_ma_fwd_infer")
+
+
+def bn_ma_backward(g2d, x2d, dx2d, slope, gslope, gbias, st: BNMAState, prop_grad: bool):
+    """gslope += sum g xhat, gbias += sum g, dx = a (g - sum g / R - xhat sum(g xhat) / R) with
+    xhat = (x - mean) inv, a = slope inv of the last training forward.  dx may alias x or g."""
+    rows, C = g2d.shape
+    if not _native_t(g2d):
+        g, x = g2d.float(), x2d.float()
+        mean, inv = st.stat[0], st.stat[2]
+        xh = (x - mean) * inv
+        sg, sgx = g.sum(0), (g * xh).sum(0)
+        gslope.add_(sgx)
+        gbias.add_(sg)
+        if prop_grad:
+            dx2d.copy_(slope * inv * (g - sg / rows - xh * sgx / rows))
+        return
+    native.check(_k().cxn_bn_ma_bwd(g2d.data_ptr(), x2d.data_ptr(), dx2d.data_ptr() if prop_grad else None,
+                                    slope.data_ptr(), gslope.data_ptr(), gbias.data_ptr(), st.stat.data_ptr(),
+                                    st.coef.data_ptr(), st.ws.data_ptr(), st.ws.numel(), rows, C, _stream()),
+                 "bn_ma_bwd")
+
+
 # ----------------------------------------------------------------------------- prelu
 def _prelu_mask_ref(x2d, slope, seed, counter, rnd):
     rows, C = x2d.shape
