@@ -1,4 +1,4 @@
-"""Float64 references and derived per-element error bounds for the convolution kernels.
+"""Float64 references and derived per-element error bounds for the convolution and GEMM kernels.
 
 A whole-tensor norm ratio cannot see a localized defect (one border pixel, the last image of an
 odd batch, one channel fragment): bf16 output rounding alone puts it at ~1.7e-3, and a dropped
@@ -15,6 +15,9 @@ derived from the arithmetic, not tuned to what a kernel gives:
   bias-gradient sum (fp32):            bound = (R + 2) 2^-23 (sum |dx| + |init|),  R = N H W
   weight gradient (fp32, onto dw0):    bound = (K + 2) 2^-23 A,  A = |dw0| + conv_weight(|x|, |dy|),
                                        K = N Ho Wo
+The fully-connected GEMMs take the same forms with K = nin (forward), nout (data gradient; its
+alpha multiply is one more rounding: K + 3) and the batch (weight gradient); the fused SGD step's
+bounds are derived in sgd_step_ref.
 
 The operands are the exact bf16 values (bf16 x bf16 products are exact in float64, and float64
 summation error is ~1e-13 relative: nothing next to 2^-23).  Everything runs on the CPU.
@@ -49,9 +52,11 @@ def _bf16_bound(ref, A, K):
 
 
 def forward_ref(x, w, b=None, *, stride=1, pad=0, groups=1, relu=False):
-    """(ref, bound), NHWC float64, of y = [relu](conv(x, w) + b) stored as bf16."""
+    """(ref, bound), NHWC float64, of y = [relu](conv(x, w) + b) stored as bf16.  pad: one number
+    or (pad_y, pad_x); the kernel [Cout][KH][KW][Cg] need not be square."""
     xn, wn = _nchw(x), _nchw(w)
     bb = _f64(b) if b is not None else None
+    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
     ref = F.conv2d(xn, wn, bb, stride=stride, padding=pad, groups=groups)
     A = F.conv2d(xn.abs(), wn.abs(), bb.abs() if bb is not None else None, stride=stride, padding=pad, groups=groups)
     K = w.shape[1] * w.shape[2] * w.shape[3]
@@ -61,14 +66,27 @@ def forward_ref(x, w, b=None, *, stride=1, pad=0, groups=1, relu=False):
     return _nhwc(ref), _nhwc(bound)
 
 
-def data_grad_ref(dy, w, *, pad=0, groups=1, mask=None):
-    """(ref, bound), NHWC float64, of the stride-1 data gradient dx = conv_transpose(dy, w) stored
-    as bf16; with mask (bool NHWC, relu'(z) of the node written) ref and bound are zero where the
-    mask is: a masked element must be exactly 0."""
+def data_grad_ref(dy, w, *, stride=1, pad=0, groups=1, mask=None, in_hw=None, add=None):
+    """(ref, bound), NHWC float64, of the data gradient dx = conv_transpose(dy, w) stored as bf16
+    (stride: the forward stride; pad one number or (pad_y, pad_x)); with mask (bool NHWC, relu'(z)
+    of the node written) ref and bound are zero where the mask is: a masked element must be
+    exactly 0.  add (NHWC, dx's shape): a second gradient summed in before the store and the
+    mask, dx = mask(conv_transpose(dy, w) + add).  in_hw = (H, W) of dx: with a stride several input sizes give dy's size, and the
+    output_padding of the transposed convolution is what the geometry implies,
+    H - ((Ho - 1) stride - 2 pad_y + KH) (0 without it, which is always right at stride 1)."""
     dn, wn = _nchw(dy), _nchw(w)
-    ref = _nhwc(F.conv_transpose2d(dn, wn, padding=pad, groups=groups))
-    A = _nhwc(F.conv_transpose2d(dn.abs(), wn.abs(), padding=pad, groups=groups))
+    py, px = (pad, pad) if isinstance(pad, int) else pad
+    op = (0, 0)
+    if in_hw is not None:
+        op = tuple(full - ((o - 1) * stride - 2 * p + k) for full, o, p, k in
+                   zip(in_hw, dy.shape[1:3], (py, px), w.shape[1:3]))
+        assert all(0 <= v < max(stride, 2) for v in op), (in_hw, op)
+    kw = dict(stride=stride, padding=(py, px), output_padding=op, groups=groups)
+    ref = _nhwc(F.conv_transpose2d(dn, wn, **kw))
+    A = _nhwc(F.conv_transpose2d(dn.abs(), wn.abs(), **kw))
     K = w.shape[1] * w.shape[2] * (w.shape[0] // groups)
+    if add is not None:  # a second gradient summed in fp32 before the store: one more term
+        ref, A, K = ref + _f64(add), A + _f64(add).abs(), K + 1
     bound = _bf16_bound(ref, A, K)
     if mask is not None:
         m = mask.detach().to("cpu", torch.float64)
@@ -91,10 +109,80 @@ def weight_grad_ref(x, dy, dw0, *, stride=1, pad=0, groups=1):
     xn, dn = _nchw(x), _nchw(dy)
     shape = (dw0.shape[0], dw0.shape[3], dw0.shape[1], dw0.shape[2])
     d0 = _f64(dw0)
+    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
     ref = d0 + _nhwc(torch.nn.grad.conv2d_weight(xn, shape, dn, stride=stride, padding=pad, groups=groups))
     A = d0.abs() + _nhwc(torch.nn.grad.conv2d_weight(xn.abs(), shape, dn.abs(), stride=stride, padding=pad, groups=groups))
     K = dy.shape[0] * dy.shape[1] * dy.shape[2]
     return ref, gamma(K) * A
+
+
+def fc_forward_ref(x, w, b=None, relu=False):
+    """(ref, bound), [B][nout] float64, of y = [relu](x . w^T + b) stored as bf16; x [B][nin],
+    w [nout][nin]: the forward bound with K = nin."""
+    x64, w64 = _f64(x), _f64(w)
+    bb = _f64(b) if b is not None else torch.zeros(w.shape[0], dtype=torch.float64)
+    ref = x64 @ w64.t() + bb
+    A = x64.abs() @ w64.abs().t() + bb.abs()
+    bound = _bf16_bound(ref, A, x.shape[1])  # (of the value before the relu, which is 1-Lipschitz)
+    return (ref.clamp_min(0) if relu else ref), bound
+
+
+def fc_data_grad_ref(dy, w, alpha=1.0, mask=None):
+    """(ref, bound), [B][nin] float64, of dx = alpha dy . w stored as bf16 (dy [B][nout],
+    w [nout][nin]): K = nout, and the multiply by alpha (an fp32 number) is one more rounding,
+    so g = (K + 3) 2^-23.  mask as in data_grad_ref."""
+    d64, w64 = _f64(dy), _f64(w)
+    a = float(torch.tensor(alpha, dtype=torch.float32))
+    ref = a * (d64 @ w64)
+    A = abs(a) * (d64.abs() @ w64.abs())
+    bound = _bf16_bound(ref, A, dy.shape[1] + 1)
+    if mask is not None:
+        m = mask.detach().to("cpu", torch.float64)
+        ref, bound = ref * m, bound * m
+    return ref, bound
+
+
+def fc_weight_grad_ref(x, dy, dw0=None):
+    """(ref, bound), [nout][nin] float64, of dw = [dw0 +] dy^T . x in fp32 (the store and the +=
+    epilogues): K = the batch, bound = (K + 2) 2^-23 (|dw0| + |dy|^T . |x|)."""
+    x64, d64 = _f64(x), _f64(dy)
+    ref, A = d64.t() @ x64, d64.abs().t() @ x64.abs()
+    if dw0 is not None:
+        ref, A = ref + _f64(dw0), A + _f64(dw0).abs()
+    return ref, gamma(x.shape[0]) * A
+
+
+def _as_f32(v):
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def sgd_step_ref(x, dy, w, m, lr, wd, mom):
+    """The fc weight gradient fused with the SGD step (EPI_F32_SGD): g = dy^T . x,
+    m' = mom m - lr (g + wd w), w' = w + m', wb = bf16(w').  Returns
+    ((m', bound), (w', bound), (wb, bound)), [nout][nin] float64; w, m are the fp32 state before
+    the step, lr / wd / mom are taken as the fp32 numbers the kernel is handed.
+
+    The computed gradient is g^ with |g^ - g| <= eg = (K + 2) 2^-23 Ag, Ag = |dy|^T . |x|, K the
+    batch (the weight-gradient bound).  m' takes at most five fp32 roundings (wd w, + g, lr ..,
+    mom m, the subtraction; fewer where they are fused), each of at most 2^-24 of an intermediate
+    no larger than S = mom |m| + lr (|g| + eg + wd |w|), and the gradient's error enters scaled by
+    lr:
+        em  = lr eg + 3 2^-23 S              (3 2^-23 = 6 2^-24 >= 5 2^-24 (1 + 2^-24)^4)
+    w' = w + m' is one more rounding of a value within em of the reference:
+        ew  = em + 2^-23 (|w'| + em)
+    and the shadow is its bf16 rounding, u = 2^-8:
+        ewb = ew + u (|w'| + ew)"""
+    x64, d64, w64, m64 = _f64(x), _f64(dy), _f64(w), _f64(m)
+    lr, wd, mom = _as_f32(lr), _as_f32(wd), _as_f32(mom)
+    g, Ag = d64.t() @ x64, d64.abs().t() @ x64.abs()
+    eg = gamma(x.shape[0]) * Ag
+    m1 = mom * m64 - lr * (g + wd * w64)
+    S = abs(mom) * m64.abs() + abs(lr) * (g.abs() + eg + abs(wd) * w64.abs())
+    em = abs(lr) * eg + 3 * EPS_F32 * S
+    w1 = w64 + m1
+    ew = em + EPS_F32 * (w1.abs() + em)
+    ewb = ew + U_BF16 * (w1.abs() + ew)
+    return (m1, em), (w1, ew), (w1, ewb)
 
 
 def violations(got, ref, bound):

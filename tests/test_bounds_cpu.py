@@ -225,3 +225,144 @@ def test_nan_is_a_violation():
     assert bounds.violations(got, ref, bound)[0] == 1
     with pytest.raises(AssertionError):
         bounds.assert_within(got, ref, bound, axes="ab")
+
+
+# ------------------------------------------------------------------ GEMM references (fc, SGD step)
+# (B, nin, nout): the shapes of tests/test_gemm_tiles_bounds_gpu.py
+FC = [(37, 200, 280), (37, 1088, 280), (5, 64, 121), (300, 72, 24), (333, 136, 72)]
+FC_IDS = ["x".join(map(str, s)) for s in FC]
+
+
+def _fc_operands(case):
+    B, nin, nout = case
+    x, w, dy = _rnd((B, nin), 11), _rnd((nout, nin), 12, 0.05), _rnd((B, nout), 13)
+    b = torch.randn(nout, generator=torch.Generator().manual_seed(14)) * 0.1
+    return x, w, dy, b
+
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("case", FC, ids=FC_IDS)
+def test_fc_forward_emulation_and_zeroed_chunk(case, relu):
+    B, nin, nout = case
+    x, w, _, b = _fc_operands(case)
+    ref, bound = bounds.fc_forward_ref(x, w, b, relu=relu)
+    emu = lambda xx: (xx.float() @ w.float().t() + b)  # noqa: E731
+    post = lambda z: (z.clamp_min(0) if relu else z).to(torch.bfloat16)  # noqa: E731
+    worst = bounds.assert_within(post(emu(x)), ref, bound, "fc forward %s" % (case,), axes="bo")
+    print("fc forward", case, "max d/bound %.3f" % worst)
+    # one 16-byte DMA of x lost: 8 k of the last batch row read as zero
+    bad = x.clone()
+    bad[B - 1, nin - 16:nin - 8] = 0
+    cnt, _, idx = bounds.violations(post(emu(bad)), ref, bound)
+    rows = torch.unravel_index(idx, ref.shape)[0]
+    live = int((ref[B - 1] > 0).sum()) if relu else nout
+    assert cnt > live // 2 and set(rows.tolist()) == {B - 1}, (cnt, live)
+
+
+@pytest.mark.parametrize("case", FC, ids=FC_IDS)
+def test_fc_data_grad_emulation_and_zeroed_chunk(case):
+    B, nin, nout = case
+    x, w, dy, _ = _fc_operands(case)
+    mask = x > 0
+    ref, bound = bounds.fc_data_grad_ref(dy, w, alpha=2.0, mask=mask)
+    emu = lambda d: ((d.float() @ w.float()) * 2.0 * mask).to(torch.bfloat16)  # noqa: E731
+    worst = bounds.assert_within(emu(dy), ref, bound, "fc data gradient %s" % (case,), axes="bi")
+    print("fc data gradient", case, "max d/bound %.3f" % worst)
+    assert torch.count_nonzero(bound[~mask]) == 0
+    bad = dy.clone()
+    bad[0, :8] = 0
+    cnt, _, idx = bounds.violations(emu(bad), ref, bound)
+    assert cnt > int(mask[0].sum()) // 2 and set(torch.unravel_index(idx, ref.shape)[0].tolist()) == {0}
+
+
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("case", FC, ids=FC_IDS)
+def test_fc_weight_grad_emulation_and_zeroed_chunk(case, acc):
+    B, nin, nout = case
+    x, _, dy, _ = _fc_operands(case)
+    dw0 = torch.randn(nout, nin, generator=torch.Generator().manual_seed(15)) if acc else None
+    ref, bound = bounds.fc_weight_grad_ref(x, dy, dw0)
+    emu = lambda xx: (dy.float().t() @ xx.float()) + (dw0 if acc else 0)  # noqa: E731
+    worst = bounds.assert_within(emu(x), ref, bound, "fc weight gradient %s" % (case,), axes="oi")
+    print("fc weight gradient", case, "max d/bound %.3g" % worst)
+    # MN-major operand: one 16-byte DMA is 8 consecutive nin columns of one batch row (one k)
+    bad = x.clone()
+    bad[B - 1, nin - 8:] = 0
+    cnt, _, idx = bounds.violations(emu(bad), ref, bound)
+    cols = torch.unravel_index(idx, ref.shape)[1]
+    assert cnt > nout * 8 // 3 and int(cols.min()) >= nin - 8, (cnt, nout * 8)
+
+
+@pytest.mark.parametrize("case", [(37, 200, 280), (333, 136, 72)], ids=["37x200x280", "333x136x72"])
+def test_sgd_step_emulation_and_zeroed_chunk(case):
+    B, nin, nout = case
+    x, _, dy, _ = _fc_operands(case)
+    g = torch.Generator().manual_seed(16)
+    w, m = torch.randn(nout, nin, generator=g) * 0.02, torch.randn(nout, nin, generator=g) * 0.01
+    lr, wd, mom = 0.01, 5e-4, 0.9
+    refs = bounds.sgd_step_ref(x, dy, w, m, lr, wd, mom)
+
+    def emu(xx):
+        grad = dy.float().t() @ xx.float()
+        m1 = mom * m - lr * (grad + wd * w)
+        w1 = w + m1
+        return m1, w1, w1.to(torch.bfloat16)
+    for name, got, (ref, bound) in zip(("m", "w", "wb"), emu(x), refs):
+        worst = bounds.assert_within(got, ref, bound, "sgd %s %s" % (name, case), axes="oi")
+        print("sgd step", case, name, "max d/bound %.3g" % worst)
+    bad = x.clone()
+    bad[B - 1, nin - 8:] = 0
+    for name, got, (ref, bound) in zip(("m", "w", "wb"), emu(bad), refs):
+        cnt, _, idx = bounds.violations(got, ref, bound)
+        cols = torch.unravel_index(idx, ref.shape)[1]
+        assert cnt > nout * 8 // 3 and int(cols.min()) >= nin - 8, (name, cnt)
+
+
+def test_conv_refs_take_tuple_padding_stride_and_nonsquare_kernels():
+    """forward_ref with a 1 x 3 kernel and (0, 1) padding, data_grad_ref with forward stride 2 at
+    a size where the output_padding is not 0, against fp32 torch (conv2d / conv2d_input)."""
+    x, w = _rnd((2, 12, 10, 32), 21), _rnd((64, 1, 3, 32), 22, 0.05)
+    ref, bound = bounds.forward_ref(x, w, None, pad=(0, 1))
+    y = _nhwc(F.conv2d(_nchw(x), _nchw(w), padding=(0, 1))).to(torch.bfloat16)
+    assert tuple(ref.shape) == (2, 12, 10, 64)
+    bounds.assert_within(y, ref, bound, "1x3 forward")
+    dy = _rnd((2, 12, 10, 64), 23)
+    ref, bound = bounds.data_grad_ref(dy, w, pad=(0, 1))
+    dx = _nhwc(torch.nn.grad.conv2d_input((2, 32, 12, 10), _nchw(w), _nchw(dy), padding=(0, 1))).to(torch.bfloat16)
+    bounds.assert_within(dx, ref, bound, "1x3 data gradient")
+    # stride 2, 3 x 3, pad 1 on 16 x 12: Ho x Wo = 8 x 6, output_padding (1, 1)
+    w, dy = _rnd((72, 3, 3, 16), 24, 0.05), _rnd((3, 8, 6, 72), 25)
+    ref, bound = bounds.data_grad_ref(dy, w, stride=2, pad=1, in_hw=(16, 12))
+    assert tuple(ref.shape) == (3, 16, 12, 16)
+    dx = _nhwc(torch.nn.grad.conv2d_input((3, 16, 16, 12), _nchw(w), _nchw(dy), stride=2, padding=1)).to(torch.bfloat16)
+    bounds.assert_within(dx, ref, bound, "strided data gradient")
+    dx[2, 15, 11] = 0  # the last row / column exists only through the output_padding
+    assert bounds.violations(dx, ref, bound)[0] > 0
+
+
+def test_emulated_gemm_gate_defects_are_located():
+    """Two defects of the implicit-GEMM tiles, emulated on geometry G4 of
+    tests/test_gemm_tiles_bounds_gpu.py (3 x 13 x 13, 2 groups of 24 -> 40 channels, 3 x 3):
+    the store gate of a 64-row tile dropped (rows 40..63 staged for group 0 are group 1's first
+    24 weight rows, and land on group 1's channels), and the K tail lost (kdim 216 = 3 K-tiles
+    and a 24 tail: the last tap's channels).  The violations name the place."""
+    x, w = _rnd((3, 13, 13, 48), 31), _rnd((80, 3, 3, 24), 32, 0.05)
+    b = torch.randn(80, generator=torch.Generator().manual_seed(33)) * 0.1
+    ref, bound = bounds.forward_ref(x, w, b, pad=1, groups=2)
+    emu = lambda ww: _nhwc(F.conv2d(_nchw(x), _nchw(ww), b, padding=1, groups=2))  # noqa: E731
+    good = emu(w).to(torch.bfloat16)
+    assert bounds.violations(good, ref, bound)[0] == 0
+    # (a) group 0's tile stores 64 rows: group 1's weight rows 0..23 against group 0's input, no bias
+    bad = good.clone()
+    bad[..., 40:64] = _nhwc(F.conv2d(_nchw(x[..., :24]), _nchw(w[40:64]), padding=1)).to(torch.bfloat16)
+    cnt, _, idx = bounds.violations(bad, ref, bound)
+    ch = torch.unravel_index(idx, ref.shape)[3]
+    assert cnt > 3 * 13 * 13 * 24 * 0.9 and int(ch.min()) == 40 and int(ch.max()) == 63
+    with pytest.raises(AssertionError, match=r"c 40\.\.63"):
+        bounds.assert_within(bad, ref, bound)
+    # (b) k = (kh, kw, c) >= 192 is tap (2, 2): every pixel that has the tap inside the image
+    tail = w.clone()
+    tail[:, 2, 2, :] = 0
+    cnt, _, idx = bounds.violations(emu(tail).to(torch.bfloat16), ref, bound)
+    n, h, ww_, c = torch.unravel_index(idx, ref.shape)
+    assert cnt > 3 * 12 * 12 * 80 // 2 and int(h.max()) == 11 and int(ww_.max()) == 11

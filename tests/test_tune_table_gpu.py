@@ -168,16 +168,48 @@ REPS = {
 }
 
 
+def _candidate_serves(op, tile):
+    """Whether forcing `tile` on the representative shape of `op` runs that tile (True), a
+    fallback kernel (False: the op's form does not compile the tile, tests/test_tile_table_cpu.py
+    served_tiles), or is decided by a shape rule outside gemm_glds.hip (None: the halo tiles,
+    tests/test_conv_halo_gpu.py)."""
+    from test_tile_table_cpu import glds_served_matrix
+    kk, mm, _ = glds_served_matrix()
+    if tile == gemm.REG:
+        return False
+    if tile in kk | mm:
+        return tile in (kk if op in ("cf", "cd", "cr", "fc") else mm)
+    if tile == 114:  # gemm_4w.hip fast_ok: a K_GATHER operand with Cg % 64 == 0, kdim % 64 == 0, <= 32 taps
+        if op not in ("cf", "cd"):
+            return False
+        N, H, W, C, Cout, KH, KW, s, py, px, G = REPS[op]
+        cg = (C if op == "cf" else Cout) // G
+        return cg % 64 == 0 and KH * KW <= 32
+    return None if op in ("cf", "cd") else False
+
+
 @pytest.mark.parametrize("tile", list(gemm.GLDS_CANDS) + [gemm.REG])
 @pytest.mark.parametrize("op", ["cf", "cd", "cw", "cr", "fc", "fw"])
-def test_every_candidate_tile(op, tile):
+def test_every_candidate_tile(op, tile, monkeypatch):
+    """A served (op, tile) pair must run the forced tile (gemm.LAST_GLDS); a pair the op's form
+    does not compile must decline it and still compute the right answer on the fallback kernel
+    (that case used to pass without saying which kernel ran)."""
     if op in ("cr", "fc", "fw") and tile == gemm.REG:
         pytest.skip("the register-kernel pseudo-tile is a candidate for conv fwd / dgrad / wgrad only")
+    if op == "cr":  # the direct row-run kernels stand in front of the row-gather GEMM whatever the tile
+        monkeypatch.setattr(gemm, "_ROWRUN_FWD2", False)
+        monkeypatch.setattr(gemm, "_ROWRUN_DIRECT", False)
+    gemm.LAST_GLDS[0] = None
     if op in REPS:
         err = check_conv(op, REPS[op], tile=tile)
     else:
         err = check_fc(op, 4096, 1000, 96, tile=tile)
     assert err < 1e-2, (op, tile, err)
+    serves = _candidate_serves(op, tile)
+    if serves:
+        assert gemm.LAST_GLDS[0] == tile, (op, tile, "the forced tile did not run", gemm.LAST_GLDS[0])
+    elif serves is False:
+        assert gemm.LAST_GLDS[0] != tile, (op, tile, "a tile the form does not compile reported that it ran")
 
 
 def test_tuner_rejects_a_wrong_fast_tile(monkeypatch):
