@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import glob
 import os
+import shutil
 import subprocess
 import sys
 import sysconfig
@@ -70,15 +71,19 @@ def build_runtime(verbose=False, force=False) -> str:
     return target
 
 
+def kernel_compile_cmd(kernel_dir):
+    """The hipcc command line (without input / output) that compiles one kernels/*.hip."""
+    return [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
+            "-munsafe-fp-atomics", "-Wno-unused-result", "-I" + kernel_dir]
+
+
 def build_kernels(verbose=False, force=False, jobs=8) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "kernels", "*.h"))
     target = os.path.join(OUT, KERNEL_LIB)
     objdir = os.path.join(OUT, "obj")
     os.makedirs(objdir, exist_ok=True)
-    common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
-              "-munsafe-fp-atomics", "-Wno-unused-result",
-              "-I" + os.path.join(CSRC, "kernels")]
+    common = kernel_compile_cmd(os.path.join(CSRC, "kernels"))
     objs = []
     jobs_list = []
     for s in srcs:
@@ -98,15 +103,25 @@ def build_kernels(verbose=False, force=False, jobs=8) -> str:
 
 def _check_stubs(lib):
     """Fail the build when a kernel's host launch stub is undefined: hipcc's host pass can drop
-    one silently (gemm_4w.hip lds_dma16), and the library would then fail only at dlopen on a
-    GPU box."""
-    nm = os.path.join(ROCM, "lib", "llvm", "bin", "llvm-nm")
-    if not os.path.exists(nm):
+    one silently (a builtin called directly inside a kernel's lambdas, see lds_dma16 in
+    gfx950_prims.h; a launch moved into a generic lambda is the same hazard), and the library would
+    then fail only at dlopen on a GPU box.  Uses ROCm's llvm-nm, else nm from PATH, else
+    llvm-readelf; skipped only when none of them exists."""
+    llvm = os.path.join(ROCM, "lib", "llvm", "bin")
+    for tool, args in ((os.path.join(llvm, "llvm-nm"), ["-D", "--undefined-only"]),
+                       (shutil.which("nm"), ["-D", "--undefined-only"]),
+                       (os.path.join(llvm, "llvm-readelf"), ["--dyn-syms", "-W"])):
+        if tool and os.path.exists(tool):
+            break
+    else:
         return
-    out = subprocess.run([nm, "-D", "--undefined-only", lib], stdout=subprocess.PIPE, text=True).stdout
-    bad = [l.split()[-1] for l in out.splitlines() if "__device_stub__" in l]
+    out = _run([tool, *args, lib], False)
+    # (readelf lists every dynamic symbol: the undefined ones have section index UND)
+    bad = [l.split()[-1] for l in out.splitlines()
+           if "__device_stub__" in l and ("readelf" not in tool or " UND " in l)]
     if bad:
         raise RuntimeError(f"build failed: {len(bad)} undefined kernel launch stub(s) in {lib}, e.g. {bad[0]}")
+    print(f"stub check ({os.path.basename(tool)}): 0 undefined __device_stub__ symbols in {KERNEL_LIB}")
 
 
 def build_wrapper(verbose=False, force=False) -> str:
@@ -171,7 +186,6 @@ def build_asan(verbose=False, force=False):
             build_kernels(verbose)
             OUT = ASAN_DIR
         if not os.path.exists(k) or os.path.getmtime(k) < os.path.getmtime(src):
-            import shutil
             shutil.copy2(src, k)
         return rt, k, w
     finally:

@@ -360,8 +360,6 @@ __global__ __launch_bounds__(NT) void bn_ma_bwd_apply(const bf16_t *g, const bf1
 
 }  // namespace
 
-#define S_ static_cast<hipStream_t>(stream)
-#define RET return hipGetLastError() == hipSuccess ? 0 : -3
 
 // Workspace floats that cover every row count up to `rows` on either path.
 CXN_API long cxn_bn_ma_ws_floats(long rows, int C) {

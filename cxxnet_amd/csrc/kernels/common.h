@@ -41,6 +41,17 @@ __device__ __forceinline__ uint4 pack8(const float *f) {
   return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
 }
 
+// Counter hash behind every on-device random draw (dropout masks, random weight init, insanity
+// slopes): a value is a pure function of (index, seed), so backward regenerates forward's draws
+// without storing them.  Mirrored bit for bit in Python (ops/nn.py _hash_u32).
+__device__ __forceinline__ uint32_t hash_u32(uint32_t x, uint32_t seed) {
+  x ^= seed * 0x9E3779B9u;
+  x ^= x >> 16; x *= 0x7FEB352Du;
+  x ^= x >> 15; x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
 // Division by a runtime-invariant divisor with a multiply-high (n < 2^31).
 struct FastDiv {
   uint32_t d, mul, shift;
@@ -105,6 +116,18 @@ __device__ __forceinline__ void tile_ij(uint32_t tile, int tiles_i, int tiles_j,
 }
 
 static inline int cdiv(long a, long b) { return static_cast<int>((a + b - 1) / b); }
+
+// Blocks of a grid-stride launch over n items: per_block items each, at least 1, at most cap.
+static inline int nblocks(long n, int per_block = 256, int cap = 256 * 16) {
+  long b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  return static_cast<int>(b > cap ? cap : b);
+}
+
+// Host side of the C ABI: every entry point takes its stream as "void *stream" and returns 0, or
+// -3 when a launch failed.
+#define S_ static_cast<hipStream_t>(stream)
+#define RET return hipGetLastError() == hipSuccess ? 0 : -3
 
 // Deterministic mode (cxn_set_deterministic): reductions that would combine partial sums with
 // atomics in a run-dependent order (cross-block channel sums, bias-grad partials) use one

@@ -43,23 +43,6 @@ void launch_db_reduce(const GEpi &E, int rows, hipStream_t s);
 
 namespace {
 
-// One 1-KiB LDS-DMA (16 bytes per lane), inline asm so that hipcc neither waits for it before the
-// current stage's ds_reads nor reorders LDS reads across it; completion is counted by hand
-// (wait_vmcnt + barrier at the end of each stage).  M0 is saved and restored in the statement.
-__device__ __forceinline__ void dma16c(rsrc_t r, uint32_t lds_addr, uint32_t voff) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(r), "s"(lds_addr) : "memory");
-}
-
-// MFMA on an accumulator pinned to AGPRs: with the builtin, hipcc kept the loop-carried tile in
-// VGPRs and copied all of it into AGPRs and back every stage (2 x 96 v_accvgpr moves per stage)
-__device__ __forceinline__ void mfma_acc(f32x4 &acc, const bf16x8 &a, const bf16x8 &b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
-constexpr int cd_fdiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-
 template <int H, int W, int KS, int IPB, int NF, int NW>
 struct Cd {
   static constexpr int P = (KS - 1) / 2, T = KS * KS, PW = W + P, VR = H + P;
@@ -78,12 +61,14 @@ struct Cd {
 };
 
 // pixel (image-relative: (img H + row) W + col) of a linear slot position, -1 on gap / separator
+// (slot_pixel of conv_wgrad_direct.hip computes the same with its guard written as img < 0; either
+// spelling in both files changes the other kernel's generated code, so each keeps its own)
 template <int H, int W, int KS, int IPB>
 __device__ __forceinline__ int cd_pixel(int lin) {
   constexpr int P = (KS - 1) / 2, PW = W + P, VR = H + P;
-  const int vrow = cd_fdiv(lin, PW) ;
+  const int vrow = fdiv_floor(lin, PW) ;
   const int col = lin - vrow * PW;
-  const int img = cd_fdiv(vrow, VR);
+  const int img = fdiv_floor(vrow, VR);
   const int row = vrow - img * VR;
   if (lin < 0 || img >= IPB || row >= H || col >= W) return -1;
   return (img * H + row) * W + col;
@@ -181,11 +166,11 @@ __global__ void __launch_bounds__(64 * (NW + NL), (SB || NW + NL == 8) ? 2 : 1) 
     const int q = dwave + DW * i;
     const uint32_t dst = lds0 + static_cast<uint32_t>(b * BUF + q * 1024);
     if constexpr (i < NDX / DW) {
-      if constexpr (!(DBG & 1)) dma16c(rx, dst, voff[i]);
+      if constexpr (!(DBG & 1)) dma16(rx, dst, voff[i]);
     } else if constexpr (DW * (i + 1) <= ND) {
-      if constexpr (!(DBG & 2)) dma16c(rw, dst, voff[i]);
+      if constexpr (!(DBG & 2)) dma16(rw, dst, voff[i]);
     } else {
-      if constexpr (!(DBG & 2)) if (q < ND) dma16c(rw, dst, voff[i]);
+      if constexpr (!(DBG & 2)) if (q < ND) dma16(rw, dst, voff[i]);
     }
   };
 
@@ -310,7 +295,7 @@ __global__ void __launch_bounds__(64 * (NW + NL), (SB || NW + NL == 8) ? 2 : 1) 
     static_for<NDPW>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       const int q = dwave + DW * i;
-      if (q < ND) dma16c(i < NDX / DW ? rx : rw, lds0 + static_cast<uint32_t>(q * 1024), voff[i]);
+      if (q < ND) dma16(i < NDX / DW ? rx : rw, lds0 + static_cast<uint32_t>(q * 1024), voff[i]);
     });
   }
   wait_vmcnt<0>();
@@ -363,7 +348,7 @@ __global__ void __launch_bounds__(64 * (NW + NL), (SB || NW + NL == 8) ? 2 : 1) 
         constexpr int q = decltype(qc)::value;
         constexpr int i = q / NF, f = q % NF;
         __builtin_amdgcn_sched_barrier(0);
-        mfma_acc(acc[i][f], wf[st][f], xf[st][i]);
+        mfma16(acc[i][f], wf[st][f], xf[st][i]);
         if constexpr (!(DBG & 8) && t + 1 < T && q % RS == RS - 1 && q / RS < NR) {
           read_one(buf, std::integral_constant<int, t + 1>{}, std::integral_constant<int, st ^ 1>{},
                    std::integral_constant<int, q / RS>{});
@@ -405,14 +390,14 @@ __global__ void __launch_bounds__(64 * (NW + NL), (SB || NW + NL == 8) ? 2 : 1) 
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-        asm volatile("" : "+a"(acc[i][f]));
+        pin<true>(acc[i][f]);
       }
     for (int s = 0; s < a.nst; ++s, ++k) stage(k);
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");  // the last inline-asm MFMAs' results
 #pragma unroll
     for (int i = 0; i < WMF; ++i)
 #pragma unroll
-      for (int f = 0; f < NF; ++f) asm volatile("" : "+a"(acc[i][f]));
+      for (int f = 0; f < NF; ++f) pin<true>(acc[i][f]);
     if constexpr (!(DBG & 32)) epilogue(k - 1);
     else if (a.N < 0) epilogue(k - 1);  // (never: keeps the accumulators live)
   }
@@ -511,7 +496,7 @@ __global__ void __launch_bounds__(256, 2) conv_direct_pair(CdArgs a) {
     uint32_t v = OOB;
     if (q < NDX) {
       const int lin = 32 * q + 16 * hl + l16 - G::XLEAD;
-      const int vrow = cd_fdiv(lin, PW), col = lin - vrow * PW, row = r0 + vrow;
+      const int vrow = fdiv_floor(lin, PW), col = lin - vrow * PW, row = r0 + vrow;
       if (row >= 0 && row < H && col < W) v = static_cast<uint32_t>(((row * W + col) * a.ldx + 8 * pl) * 2);
     } else if (q < ND) {
       const int qw = q - NDX, pr = qw / NF, f = qw - pr * NF, t = 2 * pr + hl;
@@ -531,8 +516,8 @@ __global__ void __launch_bounds__(256, 2) conv_direct_pair(CdArgs a) {
       constexpr int i = decltype(ic)::value;
       const int q = wave + 4 * i;
       const uint32_t dst = lds0 + static_cast<uint32_t>(q * 1024);
-      if (q < NDX) dma16c(rx, dst, voff[i]);
-      else if (q < ND) dma16c(rw, dst, voff[i]);
+      if (q < NDX) dma16(rx, dst, voff[i]);
+      else if (q < ND) dma16(rw, dst, voff[i]);
     });
   };
   auto shift = [](int t) { return (t / KS) * PW + (t % KS); };
@@ -550,7 +535,7 @@ __global__ void __launch_bounds__(256, 2) conv_direct_pair(CdArgs a) {
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-      asm volatile("" : "+a"(acc[i][f]));
+      pin<true>(acc[i][f]);
     }
   bf16x8 xf[2][WMF], wf[2][NF];
   auto read_one = [&](auto pc, auto sc, auto rc) __attribute__((always_inline)) {
@@ -575,7 +560,7 @@ __global__ void __launch_bounds__(256, 2) conv_direct_pair(CdArgs a) {
         constexpr int q = decltype(qc)::value;
         constexpr int i = q / NF, f = q % NF;
         __builtin_amdgcn_sched_barrier(0);
-        mfma_acc(acc[i][f], wf[st][f], xf[st][i]);
+        mfma16(acc[i][f], wf[st][f], xf[st][i]);
         if constexpr (pr + 1 < NPR && q % RS == RS - 1 && q / RS < NR) {
           read_one(std::integral_constant<int, pr + 1>{}, std::integral_constant<int, st ^ 1>{},
                    std::integral_constant<int, q / RS>{});
@@ -599,7 +584,7 @@ __global__ void __launch_bounds__(256, 2) conv_direct_pair(CdArgs a) {
 #pragma unroll
   for (int i = 0; i < WMF; ++i)
 #pragma unroll
-    for (int f = 0; f < NF; ++f) asm volatile("" : "+a"(acc[i][f]));
+    for (int f = 0; f < NF; ++f) pin<true>(acc[i][f]);
 
   // ---- epilogue (as conv_direct): 4 consecutive output channels of one slot per lane
   const int c0 = g * a.Cog + cob * 16 * NF + 4 * (lane >> 4);
@@ -780,8 +765,8 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
       uint32_t v = OOB;
       if (q < NDX) {
         const int lin = 32 * q + 16 * hl + l16 - G::XLEAD;
-        const int vrow = cd_fdiv(lin, PW), col = lin - vrow * PW;
-        const int gv = bb * R + vrow, img = cd_fdiv(gv, VR), row = gv - img * VR;
+        const int vrow = fdiv_floor(lin, PW), col = lin - vrow * PW;
+        const int gv = bb * R + vrow, img = fdiv_floor(gv, VR), row = gv - img * VR;
         if (img >= 0 && img < IPB && row < H && col < W)
           v = static_cast<uint32_t>((((img * H + row) * W + col) * a.ldx + 8 * pl) * 2);
       }
@@ -821,7 +806,7 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
         const int q = wave + 8 * i;
         if (q < NDX) {
           const uint32_t off = (NB == 2 && band_n == 1) ? vx[NB - 1][i] : vx[0][i];
-          dma16c(rx, lds0 + static_cast<uint32_t>(xb * XB + q * 1024), off);
+          dma16(rx, lds0 + static_cast<uint32_t>(xb * XB + q * 1024), off);
         }
       }
     }
@@ -832,7 +817,7 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
       if (q < NDW && pp < npp_n) {
         // the second half of an odd tap count's last pair reads zeros
         const uint32_t off = (2 * (pr0_n + pp) + 1 >= T && hl) ? OOB : vw[i];
-        dma16c(rw, lds0 + static_cast<uint32_t>(2 * XB + wb * WBF + q * 1024), off);
+        dma16(rw, lds0 + static_cast<uint32_t>(2 * XB + wb * WBF + q * 1024), off);
       }
     }
   };
@@ -947,7 +932,7 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
 #pragma unroll
       for (int f = 0; f < NFW; ++f) {
         acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-        asm volatile("" : "+a"(acc[i][f]));
+        pin<true>(acc[i][f]);
       }
     for (int r = 0; r < SPI; ++r, ++k) {
       const int h = r % NPG;
@@ -978,7 +963,7 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
             constexpr int q = decltype(qc)::value;
             constexpr int i = q / NFW, f = q % NFW;
             __builtin_amdgcn_sched_barrier(0);
-            mfma_acc(acc[i][f], wf[st][f], xf[st][i]);
+            mfma16(acc[i][f], wf[st][f], xf[st][i]);
             if constexpr (q % RS == RS - 1 && q / RS < NR) {
               if (pp + 1 < npp)
                 read_one(pr0 + pp + 1, pp + 1, std::integral_constant<int, st ^ 1>{}, std::integral_constant<int, q / RS>{});
@@ -1004,7 +989,7 @@ __global__ void __launch_bounds__(512, 2) conv_direct2(CdArgs a) {
 #pragma unroll
     for (int i = 0; i < WMF; ++i)
 #pragma unroll
-      for (int f = 0; f < NFW; ++f) asm volatile("" : "+a"(acc[i][f]));
+      for (int f = 0; f < NFW; ++f) pin<true>(acc[i][f]);
     epilogue(j);
   }
 }

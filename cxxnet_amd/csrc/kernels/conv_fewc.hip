@@ -17,16 +17,13 @@
 //   * epilogue: bias + relu in fp32, bf16, written through a per-wave LDS transpose so each
 //     pixel's Cout channels leave as whole 16-byte chunks (a wave stores 16 pixels x Cout*2 B
 //     per instruction pair instead of 8-byte pieces 128 B apart).
-#include "common.h"
+#include "gfx950_prims.h"
+
+using namespace cxg;
 
 namespace {
 
 constexpr int NT = 256;  // 4 waves
-
-__device__ __forceinline__ void lds_handoff() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // y[n][ho][wo][co] (row stride ldc) = relu?(bias[co] + sum_{ky,kx,c} w[co][ky][kx][c] x[n][ho*S-P+ky][wo*S-P+kx][c])
 template <int CF>  // output channels / 16
@@ -131,7 +128,7 @@ __global__ void __launch_bounds__(NT) conv_fewc_fwd(const bf16_t *__restrict__ x
           *reinterpret_cast<uint2 *>(st + (lane & 15) * SP + (cf * 16 + 4 * (lane >> 4)) * 2) =
               make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
         }
-        lds_handoff();
+        wave_lds_wait_handoff();
         constexpr int CH = COUT / 8;  // 16-byte chunks per pixel
 #pragma unroll
         for (int i = 0; i < (16 * CH + 63) / 64; ++i) {
@@ -143,7 +140,7 @@ __global__ void __launch_bounds__(NT) conv_fewc_fwd(const bf16_t *__restrict__ x
             if (wo < Wo) *reinterpret_cast<uint4 *>(yrow + static_cast<long>(wo) * ldc + part * 8) = v;
           }
         }
-        lds_handoff();  // staging rows are rewritten by the next column
+        wave_lds_wait_handoff();  // staging rows are rewritten by the next column
       }
     }
   }
@@ -175,7 +172,6 @@ int launch(const bf16_t *x, const bf16_t *w, const float *bias, bf16_t *y, int N
 
 }  // namespace
 
-#define S_ static_cast<hipStream_t>(stream)
 
 // 4-channel NHWC x (8-byte pixels, 8-byte aligned), w [Cout][KH][KW][4], Cout in {16, 32, 48, 64, 96,
 // 128}, ldc % 8 == 0 (16-byte aligned output rows).  -1: shape not served (caller uses the GEMM).

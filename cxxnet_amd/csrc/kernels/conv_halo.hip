@@ -26,7 +26,7 @@
 //     K-tile t+2; wait for t+1's weights; barrier; [B] k-step-1 MFMAs carrying the reads of
 //     k-step 0 of t+1 (whose weights sit in a stage nobody reads any more, hence three stages);
 //   * 4 waves (one per SIMD): BM = 64 -> 1 x 4 waves of 64 channels x 64 pixels; BM = 128 ->
-//     2 x 2 waves of 64 x 128; accumulators pinned in AGPRs (inline-asm MFMA as gemm_4w.hip);
+//     2 x 2 waves of 64 x 128; accumulators pinned in AGPRs (inline-asm MFMA: mfma16 in gfx950_prims.h);
 //   * epilogue: the 8-wave kernels' staged writer (bias, relu, relu'-mask of the old value),
 //     one 16-pixel fragment (one row segment of the patch) at a time.
 #include "gemm_glds_common.h"
@@ -38,29 +38,6 @@ void launch_db_reduce(const GEpi &E, int rows, hipStream_t s);  // gemm_glds.hip
 }
 
 namespace {
-
-__device__ __forceinline__ void lds_dma16h(const char *p, uint32_t n, char *dst, uint32_t voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(p, n), (lds_void *)dst, 16, voff, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_lgkm_h() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void mfma_h(f32x4 &acc, const bf16x8 &a, const bf16x8 &b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
-// an empty volatile asm that "rewrites" every accumulator: register code reading or writing
-// them cannot move across it, and it keeps its order with the other volatile asm
-template <int MR, int NR>
-__device__ __forceinline__ void pin_acc(f32x4 (&acc)[MR][NR]) {
-#pragma unroll
-  for (int m = 0; m < MR; ++m)
-#pragma unroll
-    for (int n = 0; n < NR; ++n) asm volatile("" : "+a"(acc[m][n]));
-}
 
 constexpr int halo_pitch(int wt) { return (wt + 2 + 7) / 8 * 8; }
 
@@ -148,7 +125,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
     uint32_t n;
     descA(cb, tap, p, n);
 #pragma unroll
-    for (int s = 0; s < NA; ++s) lds_dma16h(p, n, smem + Cf::A_OFF + stage * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
+    for (int s = 0; s < NA; ++s) lds_dma16(p, n, smem + Cf::A_OFF + stage * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
   };
   auto halo_desc = [&](int cb, const char *&p, uint32_t &n) __attribute__((always_inline)) {
     const bool in = cb < ncb;
@@ -194,7 +171,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
     uint32_t n;
     halo_desc(0, p, n);
 #pragma unroll
-    for (int s = 0; s < NHD; ++s) lds_dma16h(p, n, halo_dst(0, s), offH[s]);
+    for (int s = 0; s < NHD; ++s) lds_dma16(p, n, halo_dst(0, s), offH[s]);
     issue_A(0, 0, 0);
     issue_A(0, 1, 1);
   }
@@ -214,7 +191,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
       constexpr int st = tap % 3;
       // DMAs riding on [A]: the weights of K-tile t + 2, then (taps 0-6) NHK of the next halo's
       constexpr int NQ = NA + (tap < 7 ? NHK : 0);
-      wait_lgkm_h<0>();  // k-step-0 fragments of this K-tile
+      wait_lgkm<0>();  // k-step-0 fragments of this K-tile
       __builtin_amdgcn_sched_barrier(0);
       static_for<PER>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
@@ -224,7 +201,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
           descA(cb + (tap + 2) / 9, (tap + 2) % 9, p, n);
 #pragma unroll
           for (int s = 0; s < NA; ++s)
-            lds_dma16h(p, n, smem + Cf::A_OFF + ((tap + 2) % 3) * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
+            lds_dma16(p, n, smem + Cf::A_OFF + ((tap + 2) % 3) * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
         }
         if constexpr (NQ > NA) {  // then this K-tile's share of the next block's halo, spread out
           static_for<NHK>([&](auto jc) {
@@ -232,25 +209,25 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
             if constexpr (u == (j + 1) * PER / (NHK + 1)) {
               constexpr int hs = tap * NHK + j;  // this wave's halo DMA index
               if constexpr (hs < NHD) {
-                lds_dma16h(hp, hn, halo_dst(hb ^ 1, hs), offH[hs]);
+                lds_dma16(hp, hn, halo_dst(hb ^ 1, hs), offH[hs]);
               } else {
-                lds_dma16h(hp, 0u, smem + Cf::SINK, OOB);  // keeps the count fixed
+                lds_dma16(hp, 0u, smem + Cf::SINK, OOB);  // keeps the count fixed
               }
             }
           });
         }
-        mfma_h(acc[u / NR][u % NR], fa[0][u / NR], fb[0][u % NR]);
+        mfma16(acc[u / NR][u % NR], fa[0][u / NR], fb[0][u % NR]);
         if constexpr (u < NF) read_frag(1, u, st, hb, tap, 1);
         __builtin_amdgcn_sched_barrier(0);
       });
       // [A] -> [B]: the weights of K-tile t + 1 (and, at tap 8, the next block's halo, issued
       // before them) have landed for this wave; the barrier makes them landed for every wave
-      wait_lgkm_h<0>();
+      wait_lgkm<0>();
       wait_vmcnt<NQ>();
       block_barrier();
       static_for<PER>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
-        mfma_h(acc[u / NR][u % NR], fa[1][u / NR], fb[1][u % NR]);
+        mfma16(acc[u / NR][u % NR], fa[1][u / NR], fb[1][u % NR]);
         if constexpr (u < NF) {
           if constexpr (tap < 8) {
             read_frag(0, u, (tap + 1) % 3, hb, tap + 1, 0);
@@ -264,7 +241,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
   }
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
   wait_vmcnt<0>();
-  wait_lgkm_h<0>();
+  wait_lgkm<0>();
   __syncthreads();  // the epilogue stages through the halo buffers
 
   // epilogue: one 16-pixel fragment (one patch-row segment) at a time
@@ -277,14 +254,14 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
 #pragma unroll
     for (int m = 0; m < MR; ++m)
       *reinterpret_cast<f32x4 *>(ep + l16 * (WM + 4) + m * 16 + g4 * 4) = acc[m][n];
-    wait_lgkm_h<0>();
+    wait_lgkm<0>();
     const int p0 = wc * WN + 16 * n;
     const int h = h0 + p0 / WT, w = w0 + p0 % WT;
     const int valid = h < H ? min(16, W - w) : 0;
     const int jrow0 = (img * H + h) * W + w;
     write_staged<EPI_BF16, 16, WM>(ep, E, 0, 0, A.rows, jrow0 + max(valid, 0), i0 + wr * WM, jrow0, lane, bv8,
                                    EPI == EPI_BF16_DB ? bsum : nullptr);
-    wait_lgkm_h<0>();
+    wait_lgkm<0>();
   }
   if constexpr (EPI == EPI_BF16_DB) {
     // the lower conv's bias gradient: lanes l, l + 8, ... summed the same 8 channels; their sums
@@ -294,7 +271,7 @@ conv_halo(GOperand A, GOperand B, GEpi E, int tiles_o, int tiles_w, int tiles_h,
     static_assert(16 * (WM + 4) >= 64 * 9, "staging area holds the lane sums");
 #pragma unroll
     for (int e = 0; e < 8; ++e) ep[lane * 9 + e] = bsum[e];
-    wait_lgkm_h<0>();
+    wait_lgkm<0>();
     if (lane < LPR) {
       float *row = E.dbias + static_cast<long>(gb.tile / static_cast<uint32_t>(tiles_o) * Cf::WGN + wc) * E.part_ld;
 #pragma unroll
@@ -407,7 +384,7 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
     const uint32_t n = in ? A.nbytes - step : 0u;
 #pragma unroll
     for (int s = 0; s < NA; ++s)
-      lds_dma16h(wptr + step, n, smem + Cf::A_OFF + stage * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
+      lds_dma16(wptr + step, n, smem + Cf::A_OFF + stage * Cf::ASTAGE + (wave + 4 * s) * 1024, offA[s]);
   };
 
   const char *pa = smem + Cf::A_OFF + wr * WM * 128;
@@ -438,7 +415,7 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
   set_halo(offH, true, h0, w0, img);
   const char *const hp = reinterpret_cast<const char *>(B.ptr);
 #pragma unroll
-  for (int s = 0; s < NHD; ++s) lds_dma16h(hp, B.nbytes, halo_dst(0, s), offH[s]);
+  for (int s = 0; s < NHD; ++s) lds_dma16(hp, B.nbytes, halo_dst(0, s), offH[s]);
   issue_A(true, 0, 0, 0);
   issue_A(true, 0, 1, 1);
   wait_vmcnt<NA>();
@@ -482,7 +459,7 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
       constexpr int tap = decltype(tc)::value;
       constexpr int st = tap % 3;
       constexpr int NQ = NA + (tap < 7 ? NHK : 0);
-      wait_lgkm_h<0>();
+      wait_lgkm<0>();
       __builtin_amdgcn_sched_barrier(0);
       static_for<PER>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
@@ -495,22 +472,22 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
           if constexpr (tap < 7 && u == (j + 1) * PER / (NHK + 1)) {
             constexpr int hs = tap * NHK + j;
             if constexpr (hs < NHD) {
-              lds_dma16h(hpn, hn, halo_dst(hb ^ 1, hs), offN[hs]);
+              lds_dma16(hpn, hn, halo_dst(hb ^ 1, hs), offN[hs]);
             } else {
-              lds_dma16h(hp, 0u, smem + Cf::SINK, OOB);
+              lds_dma16(hp, 0u, smem + Cf::SINK, OOB);
             }
           }
         });
-        mfma_h(acc[u / NR][u % NR], fa[0][u / NR], fb[0][u % NR]);
+        mfma16(acc[u / NR][u % NR], fa[0][u / NR], fb[0][u % NR]);
         if constexpr (u < NF) read_frag(1, u, st, hb, tap, 1);
         __builtin_amdgcn_sched_barrier(0);
       });
-      wait_lgkm_h<0>();
+      wait_lgkm<0>();
       wait_vmcnt<NQ>();  // all but this tap's DMAs
       block_barrier();
       static_for<PER>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
-        mfma_h(acc[u / NR][u % NR], fa[1][u / NR], fb[1][u % NR]);
+        mfma16(acc[u / NR][u % NR], fa[1][u / NR], fb[1][u % NR]);
         if constexpr (u < NF) {
           if constexpr (tap < 8) {
             read_frag(0, u, (tap + 1) % 3, hb, tap + 1, 0);
@@ -527,7 +504,7 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
       // accumulators the last MFMAs had not written yet)
       asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
       pin_acc(acc);
-      wait_lgkm_h<0>();
+      wait_lgkm<0>();
       // Epilogue.  alpha, bias and relu are applied in registers; the wave's bf16 [pixel][channel]
       // image of 64 pixels (16-byte chunk c of pixel p at c ^ (p & 7)) is staged in this item's
       // dead halo buffer and leaves as 16-byte row segments.  The 8-wave kernels' staged writer
@@ -556,14 +533,14 @@ conv_halo_ps(GOperand A, GOperand B, GEpi E, int tiles_w, int tiles_h, uint32_t 
                 make_uint2(pack2(f[0], f[1]), pack2(f[2], f[3]));
           }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         uint4 q[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const int pix = (lane >> 3) + 8 * k;
           q[k] = *reinterpret_cast<const uint4 *>(eb + pix * 128 + (((lane & 7) ^ (pix & 7)) * 16));
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the next half rewrites the image)
+        wait_lgkm<0>();  // (the next half rewrites the image)
         long row[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {

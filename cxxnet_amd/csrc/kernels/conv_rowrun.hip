@@ -24,30 +24,23 @@
 //     instruction is issued (masked lanes store out of range), so the next item waits with a
 //     counted s_waitcnt for its own DMAs only, not for these stores.
 #include <cstdlib>
-#include "common.h"
+#include "gfx950_prims.h"
+
+using namespace cxg;
 
 namespace {
 
 constexpr int NT = 512;   // 8 waves, two per SIMD: one's LDS reads overlap the other's MFMAs
 constexpr int RG = 4;     // output rows per work item (one per wave pair)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void lds_void;
 
-__device__ __forceinline__ void wave_lds_handoff() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <int N_>
-__device__ __forceinline__ void vm_wait_le() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
 __device__ __forceinline__ void vm_wait(int n) {  // s_waitcnt vmcnt(n), n uniform, 0..15
   switch (n) {
-    case 0: vm_wait_le<0>(); break;  case 1: vm_wait_le<1>(); break;  case 2: vm_wait_le<2>(); break;
-    case 3: vm_wait_le<3>(); break;  case 4: vm_wait_le<4>(); break;  case 5: vm_wait_le<5>(); break;
-    case 6: vm_wait_le<6>(); break;  case 7: vm_wait_le<7>(); break;  case 8: vm_wait_le<8>(); break;
-    case 9: vm_wait_le<9>(); break;  case 10: vm_wait_le<10>(); break; case 11: vm_wait_le<11>(); break;
-    case 12: vm_wait_le<12>(); break; case 13: vm_wait_le<13>(); break; case 14: vm_wait_le<14>(); break;
-    default: vm_wait_le<15>(); break;
+    case 0: wait_vmcnt<0>(); break;  case 1: wait_vmcnt<1>(); break;  case 2: wait_vmcnt<2>(); break;
+    case 3: wait_vmcnt<3>(); break;  case 4: wait_vmcnt<4>(); break;  case 5: wait_vmcnt<5>(); break;
+    case 6: wait_vmcnt<6>(); break;  case 7: wait_vmcnt<7>(); break;  case 8: wait_vmcnt<8>(); break;
+    case 9: wait_vmcnt<9>(); break;  case 10: wait_vmcnt<10>(); break; case 11: wait_vmcnt<11>(); break;
+    case 12: wait_vmcnt<12>(); break; case 13: wait_vmcnt<13>(); break; case 14: wait_vmcnt<14>(); break;
+    default: wait_vmcnt<15>(); break;
   }
 }
 
@@ -67,8 +60,7 @@ conv_rowrun_fwd(const bf16_t *__restrict__ x, long x_bytes, const bf16_t *__rest
   char *sw = smem + 2 * XB;                // [COUT][WPB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g4 = lane >> 4, l16 = lane & 15;
-  const rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(x), (short)0,
-                                                      static_cast<int>(x_bytes), 0x00020000);
+  const rsrc_t rx = make_rsrc(x, static_cast<uint32_t>(x_bytes));
 
   const int groups_per_img = (Ho + RG - 1) / RG;
   const long items = static_cast<long>(N) * groups_per_img;
@@ -82,7 +74,7 @@ conv_rowrun_fwd(const bf16_t *__restrict__ x, long x_bytes, const bf16_t *__rest
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dst + q * 1024), 16, o, 0, 0, 0);
     }
   };
-  const rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y, (short)0, static_cast<int>(y_bytes), 0x00020000);
+  const rsrc_t ry = make_rsrc(y, static_cast<uint32_t>(y_bytes));
   long it = blockIdx.x;
   if (it < items) issue(it, 0);
 
@@ -182,7 +174,7 @@ conv_rowrun_fwd(const bf16_t *__restrict__ x, long x_bytes, const bf16_t *__rest
           *reinterpret_cast<uint2 *>(st + l16 * SPB + (cf * 16 + 4 * g4) * 2) =
               make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
         }
-        wave_lds_handoff();
+        wave_lds_wait_handoff();
         constexpr int CH = CFH * 2;  // 16-byte chunks per pixel (of this wave's channels)
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
@@ -195,12 +187,12 @@ conv_rowrun_fwd(const bf16_t *__restrict__ x, long x_bytes, const bf16_t *__rest
           typedef int v4i __attribute__((ext_vector_type(4)));
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), ry, off, 0, 0);
         }
-        wave_lds_handoff();
+        wave_lds_wait_handoff();
       }
     }
     buf ^= 1;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 }
 
 // CXXNET_ROWRUN_COUNTED=0: drain every store of an item before the next one (s_waitcnt vmcnt(0))

@@ -18,16 +18,15 @@
 // The item's RG Wo pixels form one flattened GEMM dimension and the (kh, chunk) pairs another, so
 // the MFMA waste is 17 % for AlexNet (220 of 224 pixels, 99 chunks for 363 columns) instead of
 // the 44 % of one 64-pixel row per wave with 40-element row-padded runs.
-#include "direct_common.h"
+#include "gemm_glds_common.h"
 
 using namespace cxg;
-using namespace cxd;
 
 namespace {
 
-template <int KH_, int KW_, int C_, int S_, int PAD_, int W_, int WO_, int COUT_, int RG_>
+template <int KH_, int KW_, int C_, int STRIDE_, int PAD_, int W_, int WO_, int COUT_, int RG_>
 struct RGeo {
-  static constexpr int KH = KH_, KW = KW_, C = C_, S = S_, PAD = PAD_, W = W_, WO = WO_, COUT = COUT_, RG = RG_;
+  static constexpr int KH = KH_, KW = KW_, C = C_, S = STRIDE_, PAD = PAD_, W = W_, WO = WO_, COUT = COUT_, RG = RG_;
   static constexpr int SROWB = W * C * 2;                                   // source row bytes
   static constexpr int LPX = PAD == 0 ? 0 : (PAD + 1) / 2 * 2;             // staged zero pixels in front
   static constexpr int LW = PAD == 0 ? W : (LPX + W + PAD + 1) / 2 * 2;     // staged row pixels
@@ -166,11 +165,11 @@ conv_wgrad_rowrun(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
   auto issue_one = [&](int b, auto ic) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const int q = wave + 8 * i;
-    if (q < NXQ) dma16d(rx, lds0 + static_cast<uint32_t>(b * BUF + q * 1024), xs.offset(i, row0, H));
-    else if (q < NQ) dma16d(rd, lds0 + static_cast<uint32_t>(b * BUF + XB + (q - NXQ) * 1024), vd[i]);
+    if (q < NXQ) dma16(rx, lds0 + static_cast<uint32_t>(b * BUF + q * 1024), xs.offset(i, row0, H));
+    else if (q < NQ) dma16(rd, lds0 + static_cast<uint32_t>(b * BUF + XB + (q - NXQ) * 1024), vd[i]);
   };
 
-  // fragment addresses: K row (pixel) of lane for read hl: sl (frag_d's permutation), columns 4 p..
+  // fragment addresses: K row (pixel) of lane for read hl: sl (frag_tr's permutation), columns 4 p..
   const int l16 = lane & 15, g4 = lane >> 4, p4 = l16 & 3;
   int pa[NK][2];  // x: row(S oy_local) + RUN0 + 2 S C ox of pixel 32 k + sl
 #pragma unroll
@@ -206,17 +205,17 @@ conv_wgrad_rowrun(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
     for (int tt = 0; tt < TPW; ++tt) {
       acc[j][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      asm volatile("" : "+a"(acc[j][tt]));
+      pin<true>(acc[j][tt]);
     }
   bf16x8 fa[2][MTW], fb[2][TPW];
   constexpr int NR = MTW + TPW, NM = MTW * TPW, RS = NM / NR > 0 ? NM / NR : 1;
   auto read_one = [&](const char *buf, auto kc, auto sc, auto rc) __attribute__((always_inline)) {
     constexpr int k = decltype(kc)::value, st = decltype(sc)::value, r = decltype(rc)::value;
     if constexpr (r < MTW) {
-      fa[st][r] = frag_d(buf + da[r][0] + 32 * k * PB, buf + da[r][1] + 32 * k * PB);
+      fa[st][r] = frag_tr(buf + da[r][0] + 32 * k * PB, buf + da[r][1] + 32 * k * PB);
     } else {
       constexpr int tt = r - MTW;
-      fb[st][tt] = frag_d(buf + pa[k][0] + ca[tt], buf + pa[k][1] + ca[tt]);
+      fb[st][tt] = frag_tr(buf + pa[k][0] + ca[tt], buf + pa[k][1] + ca[tt]);
     }
   };
 
@@ -238,7 +237,7 @@ conv_wgrad_rowrun(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
         constexpr int q = decltype(qc)::value;
         constexpr int tt = q / MTW, j = q % MTW;
         __builtin_amdgcn_sched_barrier(0);
-        if (tt < ntn) mfma_d<true>(acc[j][tt], fa[s0][j], fb[s0][tt]);
+        if (tt < ntn) mfma16(acc[j][tt], fa[s0][j], fb[s0][tt]);
         static_for<NQW>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
           // the next item's DMAs go out during the first K-step (one after each MFMA): its
@@ -266,7 +265,7 @@ conv_wgrad_rowrun(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
   for (int j = 0; j < MTW; ++j)
 #pragma unroll
-    for (int tt = 0; tt < TPW; ++tt) pin_d<true>(acc[j][tt]);
+    for (int tt = 0; tt < TPW; ++tt) pin<true>(acc[j][tt]);
   // partial tile: ws[block][mt][nt][lane] (f32x4)
   float *out = ws + static_cast<long>(blockIdx.x) * R::SLAB + 4 * lane;
 #pragma unroll
@@ -363,10 +362,6 @@ struct Rf {
   static_assert(NK >= 3 && NST <= 60, "pipeline");
 };
 
-__device__ __forceinline__ void mfma_z(f32x4 &acc, const bf16x8 &a, const bf16x8 &b) {  // acc = a b
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
-}
-
 template <class G>
 __global__ void __launch_bounds__(512, 1)
 conv_rowrun_fwd2(const bf16_t *__restrict__ x, const bf16_t *__restrict__ w, const float *__restrict__ bias,
@@ -400,7 +395,7 @@ conv_rowrun_fwd2(const bf16_t *__restrict__ x, const bf16_t *__restrict__ w, con
   auto issue_one = [&](int b, auto ic) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const int q = wave + 8 * i;
-    if (q < NXQ) dma16d(rx, lds0 + static_cast<uint32_t>(WB + b * XB + q * 1024), xs.offset(i, row0, H));
+    if (q < NXQ) dma16(rx, lds0 + static_cast<uint32_t>(WB + b * XB + q * 1024), xs.offset(i, row0, H));
   };
   if (ib < ie) {
     prep(ib);
@@ -503,7 +498,7 @@ conv_rowrun_fwd2(const bf16_t *__restrict__ x, const bf16_t *__restrict__ w, con
         __builtin_amdgcn_sched_barrier(0);
         const bf16x8 &av = afrag(kc, std::integral_constant<int, s0>{}, std::integral_constant<int, j>{});
         if constexpr (k == 0) mfma_z(acc[j][tt], av, fb[s0][tt]);
-        else mfma_d<true>(acc[j][tt], av, fb[s0][tt]);
+        else mfma16(acc[j][tt], av, fb[s0][tt]);
         static_for<NQW>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
           // the next item's DMAs go out during the first K-step (one after each MFMA): its
@@ -531,7 +526,7 @@ conv_rowrun_fwd2(const bf16_t *__restrict__ x, const bf16_t *__restrict__ w, con
     for (int tt = 0; tt < TPW; ++tt)
 #pragma unroll
       for (int j = 0; j < MTW; ++j) {
-        pin_d<true>(acc[j][tt]);
+        pin<true>(acc[j][tt]);
         float f[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {

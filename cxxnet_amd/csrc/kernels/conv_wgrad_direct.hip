@@ -28,10 +28,9 @@
 //     read the same images share an L2.  No atomics: each block stores its partial tile with
 //     plain coalesced 16-byte stores into a workspace, and conv_wgrad_direct_reduce sums the
 //     splits in a fixed order into dW (+=), so the result is bitwise reproducible.
-#include "direct_common.h"
+#include "gemm_glds_common.h"
 
 using namespace cxg;
-using namespace cxd;
 
 namespace {
 
@@ -62,6 +61,7 @@ struct Wd {
 };
 
 // (image, row, col) of a linear position in a stage's virtual slot space; -1 when it is padding
+// (the twin of cd_pixel in conv_direct.hip, whose guard is written lin < 0: see there)
 template <int H, int W, int KS, int IPS>
 __device__ __forceinline__ int slot_pixel(int lin) {
   using G = Wd<H, W, KS, IPS>;
@@ -128,10 +128,10 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
     constexpr int i = decltype(ic)::value;
     const uint32_t base = lds0 + b * BUF + wave * 1024;  // wave-uniform LDS byte address
     if constexpr (i < NQD) {
-      dma16d(rd, base + i * 4096, vd[i]);
+      dma16(rd, base + i * 4096, vd[i]);
     } else {
       constexpr int k = i - NQD;
-      if (wave + 4 * k < CI_U * NX) dma16d(rx, base + DYB + k * 4096, vx[k]);
+      if (wave + 4 * k < CI_U * NX) dma16(rx, base + DYB + k * 4096, vx[k]);
     }
   };
   auto issue = [&](int st, int b) __attribute__((always_inline)) {
@@ -177,13 +177,13 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
     for (int m = 0; m < CO_U; ++m) {
       const int off = (m * NKS + 128 * j) * 32;
-      fa[set][m] = frag_d(smem + bd[b][0] + off, smem + bd[b][1] + off);
+      fa[set][m] = frag_tr(smem + bd[b][0] + off, smem + bd[b][1] + off);
     }
   };
   auto read_bu = [&](int set, int b, int j, int t, int u) __attribute__((always_inline)) {
     const int kh = t / KS, kw = t - kh * KS;
     const int off = (u * NXS + 128 * j + kh * PW + kw) * 32;
-    fb[set][u] = frag_d(smem + bx[b][0] + off, smem + bx[b][1] + off);
+    fb[set][u] = frag_tr(smem + bx[b][0] + off, smem + bx[b][1] + off);
   };
   auto read_b = [&](int set, int b, int j, int t) __attribute__((always_inline)) {
 #pragma unroll
@@ -223,19 +223,19 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
         // wait for tap t (and at t = 0 the K-step's dy): what may stay in flight is the reads
         // issued after them
         if constexpr (t == T - 1) {
-          if constexpr (more) wait_lgkm_d<2 * CI_U + 2 * CO_U>();
-          else wait_lgkm_d<0>();
+          if constexpr (more) wait_lgkm<2 * CI_U + 2 * CO_U>();
+          else wait_lgkm<0>();
         } else if constexpr (t == T - 2 && !more) {
-          wait_lgkm_d<2 * CI_U>();
+          wait_lgkm<2 * CI_U>();
         } else {
-          wait_lgkm_d<2 * CI_U>();
+          wait_lgkm<2 * CI_U>();
         }
         __builtin_amdgcn_sched_barrier(0);
         static_for<CO_U * CI_U>([&](auto uc) {
           constexpr int q = decltype(uc)::value;
           constexpr int m = q / CI_U, u = q % CI_U;
           constexpr int ai = (m * CI_U + u) * T + t;
-          mfma_d<(ai < NAGPR_ACC)>(acc[ai], fa[ja][m], fb[sb3][u]);
+          mfma16<(ai < NAGPR_ACC)>(acc[ai], fa[ja][m], fb[sb3][u]);
           if constexpr ((V & 1) && j == 0 && q == 4) {
             static_for<NDMA>([&](auto ic) {
               constexpr int i = decltype(ic)::value;
@@ -289,10 +289,10 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");  // inline-asm MFMA results
   static_for<G::NACC>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    pin_d<(i < NAGPR_ACC)>(acc[i]);
+    pin<(i < NAGPR_ACC)>(acc[i]);
   });
 #pragma unroll
-  for (int m = 0; m < CO_U; ++m) pin_d<false>(accb[m]);
+  for (int m = 0; m < CO_U; ++m) pin<false>(accb[m]);
 
   // ---- the four waves' partial tiles meet through LDS (both stage buffers are free: the last
   // stage ended with a barrier), CH accumulators at a time so that no more than a few sums are
@@ -440,7 +440,7 @@ long ws_wd(int N, int Cg, int Cog, int groups, int splits) {
 // 27 rows): dy rows of the band (rows past it read zeros, so a band's slots never count a
 // neighbour's pixels), x rows of the band plus the halo (rows off the map read zeros: two
 // per-lane offset sets, one per band).  LDS images and fragment reads as above
-// ([unit][slot][16 ch], ds_read_b64_tr_b16 pairs with the slot permutation of frag_d).
+// ([unit][slot][16 ch], ds_read_b64_tr_b16 pairs with the slot permutation of frag_tr).
 template <int H, int W, int KS, int R, int CO_U, int NWV>
 struct Wt {
   static constexpr int P = (KS - 1) / 2, T = KS * KS, PW = W + P;
@@ -524,11 +524,11 @@ conv_wgrad_taps(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, flo
     constexpr int i = decltype(ic)::value;
     const int q = wave + NWV * i;
     const uint32_t off = (NB == 2 && bsel == 1) ? vq[NB - 1][i] : vq[0][i];
-    if (q < NQD) dma16d(rd, lds0 + static_cast<uint32_t>(b * BUF + q * 1024), off);
-    else if (q < NQ) dma16d(rx, lds0 + static_cast<uint32_t>(b * BUF + DYB + (q - NQD) * 1024), off);
+    if (q < NQD) dma16(rd, lds0 + static_cast<uint32_t>(b * BUF + q * 1024), off);
+    else if (q < NQ) dma16(rx, lds0 + static_cast<uint32_t>(b * BUF + DYB + (q - NQD) * 1024), off);
   };
 
-  // fragment read bases (frag_d's slot permutation); A = dy unit m at K-step k: (m NKS + 32 k) 32,
+  // fragment read bases (frag_tr's slot permutation); A = dy unit m at K-step k: (m NKS + 32 k) 32,
   // B = x at K-step k under tap t: DYB + (32 k + shift(t)) 32
   const int l16 = lane & 15, g4 = lane >> 4;
   int bo[2];
@@ -543,7 +543,7 @@ conv_wgrad_taps(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, flo
 #pragma unroll
     for (int tt = 0; tt < TPW; ++tt) {
       acc[m][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      asm volatile("" : "+a"(acc[m][tt]));
+      pin<true>(acc[m][tt]);
     }
   const int ntap = tg + 4 * (TPW - 1) < T ? TPW : TPW - 1;  // this wave's tap count
   bf16x8 fa[2][CO_U], fb[2][TPW];
@@ -552,12 +552,12 @@ conv_wgrad_taps(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, flo
     constexpr int st = decltype(sc)::value, r = decltype(rc)::value;
     if constexpr (r < CO_U) {
       const int off = (r * NKS + 32 * k) * 32;
-      fa[st][r] = frag_d(buf + bo[0] + off, buf + bo[1] + off);
+      fa[st][r] = frag_tr(buf + bo[0] + off, buf + bo[1] + off);
     } else {
       constexpr int tt = r - CO_U;
       const int t = tg + 4 * tt < T ? tg + 4 * tt : tg;  // (a missing tap reads anything finite)
       const int off = DYB + (32 * k + (t / KS) * PW + (t % KS)) * 32;
-      fb[st][tt] = frag_d(buf + bo[0] + off, buf + bo[1] + off);
+      fb[st][tt] = frag_tr(buf + bo[0] + off, buf + bo[1] + off);
     }
   };
 
@@ -583,7 +583,7 @@ conv_wgrad_taps(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, flo
         constexpr int q = decltype(qc)::value;
         constexpr int tt = q / CO_U, m = q % CO_U;
         __builtin_amdgcn_sched_barrier(0);
-        if (valid && tt < ntap) mfma_d<true>(acc[m][tt], fa[s0][m], fb[s0][tt]);
+        if (valid && tt < ntap) mfma16(acc[m][tt], fa[s0][m], fb[s0][tt]);
         static_for<NQW>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
           constexpr int js = i * (NJ - 1) / NQW, first = (js * NQW + NJ - 2) / (NJ - 1);
@@ -610,7 +610,7 @@ conv_wgrad_taps(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, flo
 #pragma unroll
   for (int m = 0; m < CO_U; ++m)
 #pragma unroll
-    for (int tt = 0; tt < TPW; ++tt) pin_d<true>(acc[m][tt]);
+    for (int tt = 0; tt < TPW; ++tt) pin<true>(acc[m][tt]);
   if constexpr (NP == 2) {  // the odd-K-step waves hand their sums to the even ones through LDS
     static_assert(4 * TPW * CO_U * 1024 <= 2 * BUF, "LDS combine");
     block_barrier();  // every wave is done with the stage buffers

@@ -19,7 +19,7 @@
 //   * 4 waves (one per SIMD), wave w owns input channels 16w..16w+15 of the pair: per K-step
 //     it reads 4 dy fragments and 9 halo fragments (one per tap) and issues 36 MFMAs into
 //     4 x 9 accumulators pinned in AGPRs (144 registers) that live across all its patches;
-//   * double-buffered: the next patch's 46 DMAs are issued (12 per wave, inline asm: see dma16w)
+//   * double-buffered: the next patch's 46 DMAs are issued (12 per wave, inline asm: see dma16)
 //     as a patch starts, one barrier per patch, at its end; fragment reads of K-step r + 1 ride on
 //     the MFMAs of K-step r;
 //   * persistent split over pixels: (pairs x splits) ~ one block per CU, consecutive blocks
@@ -31,38 +31,8 @@ using namespace cxg;
 
 namespace {
 
-// One 1-KiB LDS-DMA (16 bytes per lane) as inline asm.  With the builtin, hipcc cannot tell the
-// next patch's LDS bytes from the ones the current patch's ds_reads touch and puts a vmcnt(0)
-// before the first ds_read after the DMAs: every patch then waited for all of the next patch's
-// HBM loads at its first K-step instead of letting them land under its 144 MFMAs.  Completion
-// is counted by hand (wait_vmcnt + barrier at the patch end).  M0 is saved and restored inside
-// the statement (compiler-reserved).
-__device__ __forceinline__ void dma16w(rsrc_t r, uint32_t lds_addr, uint32_t voff) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(r), "s"(lds_addr) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_lgkm_w() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void mfma_w(f32x4 &acc, const bf16x8 &a, const bf16x8 &b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
 // 32-byte unit permutation key of pixel slot s (bits 1-3 of s)
 __host__ __device__ constexpr int wg_key(int s) { return ((s >> 1) ^ ((s >> 3) << 1)) & 3; }
-
-// two transposed 8-byte reads (k-rows k and k + 4) -> one 16x16x32 operand fragment
-__device__ __forceinline__ bf16x8 frag_tr(const char *p0, const char *p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p1));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 template <int WT>
 struct WgCfg {
@@ -159,7 +129,7 @@ conv_wgrad_halo(GOperand X, GOperand D, GEpi E, int npairs, int ncib, int per, i
     const int gr = r0 + drow, gc = c0 + dcol[s];
     const bool ok = static_cast<unsigned>(gr) < static_cast<unsigned>(HH) && static_cast<unsigned>(gc) < static_cast<unsigned>(WW);
     const uint32_t pix = static_cast<uint32_t>((img * HH + gr) * WW + gc);
-    dma16w(rs, lds0 + static_cast<uint32_t>(b * BUF + dst), ok ? pix * pb + loff[s] : OOB);
+    dma16(rs, lds0 + static_cast<uint32_t>(b * BUF + dst), ok ? pix * pb + loff[s] : OOB);
   };
 
   // fragment read bases (bytes) per buffer: lane (l16, g4) reads k-rows pk and pk + 4
@@ -221,7 +191,7 @@ conv_wgrad_halo(GOperand X, GOperand D, GEpi E, int npairs, int ncib, int per, i
     static_for<KS>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
       constexpr int cur = r & 1, nxt = cur ^ 1;
-      wait_lgkm_w<0>();
+      wait_lgkm<0>();
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (r == 0) {
         if (next) static_for<ND>([&](auto sc) { issue(sc, B ^ 1, img, r0, c0); });
@@ -229,7 +199,7 @@ conv_wgrad_halo(GOperand X, GOperand D, GEpi E, int npairs, int ncib, int per, i
       __builtin_amdgcn_sched_barrier(0);
       static_for<36>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
-        mfma_w(acc[u / 9][u % 9], fa[cur][u / 9], fb[cur][u % 9]);
+        mfma16(acc[u / 9][u % 9], fa[cur][u / 9], fb[cur][u % 9]);
         if constexpr (r + 1 < KS) {
           static_for<13>([&](auto jc) {
             constexpr int j = decltype(jc)::value;

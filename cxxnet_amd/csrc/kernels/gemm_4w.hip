@@ -40,29 +40,6 @@ using namespace cxg;
 
 namespace {
 
-// One 1-KiB LDS-DMA (16 bytes per lane) through a descriptor built from (base, records).  A free
-// function on purpose: with the builtin called directly inside the kernel's lambdas, hipcc's host
-// pass silently dropped the kernel's launch stub (undefined __device_stub__ at load time).
-__device__ __forceinline__ void lds_dma16(const char *p, uint32_t n, char *dst, uint32_t voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(p, n), (lds_void *)dst, 16, voff, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_lgkm() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// MFMA with the accumulator pinned in its AGPRs ("+a"): the builtin let hipcc rotate the
-// loop-carried accumulators through other registers.  Hazards hipcc does not pad for inline asm:
-// the A/B operands come only from ds_read (waited with lgkmcnt; benchmarks/asm_audit.py checks
-// that no VALU writes them in the loop); the reads of the accumulators after the loop are padded.
-__device__ __forceinline__ void mfma16(f32x4 &acc, const bf16x8 &a, const bf16x8 &b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma32(f32x16 &acc, const bf16x8 &a, const bf16x8 &b) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-
 template <int MF>
 struct Acc;
 template <>

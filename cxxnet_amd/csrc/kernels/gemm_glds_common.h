@@ -1,15 +1,12 @@
 // Shared pieces of the LDS-DMA GEMM kernels (gemm_glds.hip, gemm_4w.hip): operand records,
 // epilogue record, LDS-DMA loaders, fragment readers and the 8-wave epilogue.
 #pragma once
-#include <utility>
-#include "common.h"
+#include "gfx950_prims.h"
 
 namespace cxg {
 
 constexpr int BK = 64;
 constexpr uint32_t OOB = 0x80000000u;  // >= num_records: the load returns zeros
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void lds_void;
 
 enum { K_DIRECT = 0, K_GATHER = 1, MN_DIRECT = 2, MN_GATHER = 3, K_ROWGATHER = 4 };
 // EPI_BF16_DB: the bf16 epilogue that also sums its stored output per column i -- a conv
@@ -84,43 +81,19 @@ __device__ __forceinline__ float sgd_step(const SgdHyp &h, float g, float &m, fl
   return w + m;
 }
 
-__device__ __forceinline__ rsrc_t make_rsrc(const void *p, uint32_t nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, static_cast<int>(nbytes), 0x00020000);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-// f(std::integral_constant<int, i>) for i = 0..N-1, fully unrolled with constant indices
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // Lanes of ONE wave hand data to each other through LDS in the epilogues (stage the fp32 tile,
 // then read whole rows).  In the per-lane memory model that is a race unless fenced: when some
 // lanes sit out the row loop (WM = 48 / 96: 60 of 64 lanes busy) hipcc hoisted the idle lanes'
 // next staging stores above the other lanes' reads (96-row tiles: rows 12-15 x 12-15 of every
 // 16 x 16 block wrong).  Fence + wave barrier pin the order; emitted only for those tile
-// widths so the kernels of the shipped table keep their code.
+// widths so the kernels of the shipped table keep their code.  (The fence form; the wait-count
+// form for a wave that only needs its own LDS operations done is wave_lds_wait_handoff.)
 template <bool ON>
 __device__ __forceinline__ void wave_lds_handoff() {
   if constexpr (ON) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-}
-
-__device__ __forceinline__ void block_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 constexpr bool kmajor(int mode) { return mode == K_DIRECT || mode == K_GATHER || mode == K_ROWGATHER; }
@@ -289,11 +262,7 @@ __device__ __forceinline__ bf16x8 frag(const char *tile, int base, int kk, int l
     const int f = (i >> 2) | ((gq & 1) << 2);              // swizzle/2 of both k-rows
     const int ch = ((base >> 4) ^ f) * 2 + ((i & 3) >> 1);  // (2*(base/16) + h) ^ 2f
     const char *p0 = tile + (kk + 8 * gq + (i >> 2)) * 256 + ch * 16 + (i & 1) * 8;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0 + 4 * 256));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return frag_tr(p0, p0 + 4 * 256);
   }
 }
 

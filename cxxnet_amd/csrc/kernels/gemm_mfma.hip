@@ -22,7 +22,9 @@
 // Epilogue is staged through LDS so every global store / atomic is a full contiguous row.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "gfx950_prims.h"
+
+using namespace cxg;
 
 namespace {
 
@@ -79,10 +81,6 @@ __device__ __forceinline__ V load_vec(const bf16_t *p) { return *reinterpret_cas
 // Buffer loads: 32-bit byte offsets against a wave-uniform resource descriptor; an
 // offset past num_records returns zeros, so padding / ragged edges need no branches.
 constexpr uint32_t OOB = 0xFFFFFF00u;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *p, uint32_t nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, static_cast<int>(nbytes), 0x00020000);
-}
 __device__ __forceinline__ uint4 bload(rsrc_t r, uint32_t off, uint4) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -274,11 +272,7 @@ __device__ __forceinline__ bf16x8 load_frag(const bf16_t *lds, int row, int kk) 
     const int k = kk + 8 * g + (i >> 2);
     const bf16_t *p0 = lds + mn_off<R>(k, row + 4 * (i & 3));
     const bf16_t *p1 = lds + mn_off<R>(k + 4, row + 4 * (i & 3));
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p1));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return frag_tr(reinterpret_cast<const char *>(p0), reinterpret_cast<const char *>(p1));
   }
 }
 

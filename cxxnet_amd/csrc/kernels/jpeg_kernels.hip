@@ -230,8 +230,6 @@ __global__ void __launch_bounds__(64) jpeg_color2(const uint8_t *__restrict__ pl
 
 }  // namespace
 
-#define S_ static_cast<hipStream_t>(stream)
-#define RET return hipGetLastError() == hipSuccess ? 0 : -3
 
 // coef int16 [nblk][64] (16-byte aligned), bwin int32 [nblk], meta int32 [B][3][80], plane uint8 [nblk][64]
 CXN_API int cxn_jpeg_idct(const void *coef, const int *bwin, const int *meta, long nblk, void *plane, void *stream) {

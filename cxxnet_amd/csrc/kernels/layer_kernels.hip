@@ -15,24 +15,11 @@ namespace {
 
 constexpr int NT = 256;
 
-__device__ __forceinline__ uint32_t hash_u32(uint32_t x, uint32_t seed) {
-  x ^= seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x7FEB352Du;
-  x ^= x >> 15; x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
 __device__ __forceinline__ uint32_t eff_seed(uint32_t seed, const int *counter) {
   return counter ? hash_u32(static_cast<uint32_t>(*counter), seed) : seed;
 }
 __device__ __forceinline__ float u01(uint32_t idx, uint32_t seed) {
   return static_cast<float>(hash_u32(idx, seed)) * 2.3283064365386963e-10f;  // [0, 1)
-}
-
-static inline int nblocks(long n, int cap = 256 * 16) {
-  long b = (n + NT - 1) / NT;
-  if (b < 1) b = 1;
-  return static_cast<int>(b > cap ? cap : b);
 }
 
 // ------------------------------------------------------------------ parameter initialisation
@@ -265,14 +252,12 @@ __global__ void ins_pool_bwd(const bf16_t *__restrict__ x, const bf16_t *__restr
 
 }  // namespace
 
-#define S_ static_cast<hipStream_t>(stream)
-#define RET return hipGetLastError() == hipSuccess ? 0 : -3
 
 // out must hold 3*C floats; it is zeroed here.
 CXN_API int cxn_rand_fill(float *out, long n, unsigned seed, int dist, float a, float b, void *stream) {
   if (n < 0 || n > 0x7fffffffL) return -1;
   if (n == 0) return 0;
-  CXN_LAUNCH((rand_fill), nblocks(n, 256 * 64), NT, 0, S_, out, static_cast<uint32_t>(n), seed, dist, a, b);
+  CXN_LAUNCH((rand_fill), nblocks(n, NT, 256 * 64), NT, 0, S_, out, static_cast<uint32_t>(n), seed, dist, a, b);
   RET;
 }
 CXN_API int cxn_chan_reduce(const void *x, const void *g, const float *mean, float *out, long rows, int C, int mode,

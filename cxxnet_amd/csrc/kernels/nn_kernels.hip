@@ -8,6 +8,8 @@
 //   dropout     : counter-hash mask, no mask storage (reference src/layer/dropout_layer-inl.hpp:44-57)
 //   softmax     : row softmax + (p - onehot) * scale grad on device (reference loss/softmax_layer-inl.hpp)
 //   bias grad   : column sums of an [rows][C] bf16 matrix into fp32 (reference K5/K11)
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -16,12 +18,6 @@ constexpr int NT = 256;
 
 __device__ __forceinline__ int grid_stride_start() { return blockIdx.x * blockDim.x + threadIdx.x; }
 __device__ __forceinline__ int grid_stride() { return gridDim.x * blockDim.x; }
-
-static inline int nblocks(long n, int per_block = NT, int cap = 256 * 16) {
-  long b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return static_cast<int>(b > cap ? cap : b);
-}
 
 // ------------------------------------------------------------------ layout
 // x: NCHW fp32 [N][C][H][W] -> y: NHWC bf16 [N][H][Wp][Cp] (channels >= C zero-filled; columns
@@ -144,7 +140,7 @@ __global__ void __launch_bounds__(NT)
 image_u8c3_nhwc3p(const uint32_t *__restrict__ pix, long ndw, const float *__restrict__ cm,
                   const float *__restrict__ mean, FastDiv fd_qpr, FastDiv fd_h, int w, int Wp,
                   int mode, float scale, uint32_t total, uint2 *__restrict__ y) {
-  __shared__ uint2 stage[NT * 3];
+  __shared__ __attribute__((aligned(16))) uint2 stage[NT * 3];
   const uint32_t q0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u);  // first group of this wave
   const uint32_t q = q0 + (threadIdx.x & 63u);
   if (q0 >= total) return;  // whole wave past the end
@@ -1675,13 +1671,6 @@ __global__ void act_bwd(const bf16_t *y, const bf16_t *dy, bf16_t *dx, long n, i
 // ------------------------------------------------------------------ dropout
 // keep iff hash(seed, i) < pkeep * 2^32; x *= keep / pkeep.  The same call with the same
 // seed in backward regenerates the mask, so no mask tensor is stored.
-__device__ __forceinline__ uint32_t hash_u32(uint32_t x, uint32_t seed) {
-  x ^= seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x7FEB352Du;
-  x ^= x >> 15; x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
 __global__ void dropout_apply(const bf16_t *x, bf16_t *y, long n, uint32_t seed0, const int *counter,
                               uint32_t thresh, float scale) {
   // counter (device, nullable) lets a captured HIP graph draw a fresh mask every replay
@@ -1964,7 +1953,6 @@ __global__ void splitk_accumulate(const float *__restrict__ ws, int nsplit, long
   }
 }
 
-__device__ __forceinline__ uint32_t hash_u32(uint32_t x, uint32_t seed);
 // DROP: the dropout layer behind a fused fc -> relu is applied here as well (keep iff
 // hash(seed, flat index) < thresh, kept values * scale), with dropout_apply's mask
 template <bool DROP>
@@ -2317,8 +2305,30 @@ __global__ void metric_accum(const float *__restrict__ part, int nb, int nm, dou
 }  // namespace
 
 // ================================================================== C ABI
-#define S_ static_cast<hipStream_t>(stream)
-#define RET return hipGetLastError() == hipSuccess ? 0 : -3
+
+// Runtime value -> template argument: f(std::integral_constant<int, h>) for the LRN half-window
+// h = 0..4 (every caller has rejected larger windows; the default arm is 4), f(std::true_type /
+// std::false_type) for a flag.  f is a generic lambda holding one CXN_LAUNCH.
+template <typename F>
+static inline void with_half(int half, F &&f) {
+  switch (half) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+template <typename F>
+static inline void with_flag(bool on, F &&f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+// dropout keeps element i iff hash_u32(i, seed) < pkeep * 2^32 (saturated)
+static inline uint32_t dropout_thresh(float pkeep) {
+  const double t = static_cast<double>(pkeep) * 4294967296.0;
+  return t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t);
+}
 
 // Wp: the node's physical row width (>= W; row-padded first-conv input, see image_u8c3_nhwc3p)
 CXN_API int cxn_nchw_f32_to_nhwc_bf16(const float *x, void *y, int N, int C, int H, int W, int Cp, int Wp,
@@ -2429,26 +2439,18 @@ CXN_API int cxn_pool_fwd(const void *x, void *y, void *arg, int N, int H, int W,
       (const bf16_t *)x, (bf16_t *)y, (uint8_t *)arg, H, W, C, Ho, Wo, KH, KW, S, P, mode, relu,             \
       make_fastdiv(static_cast<uint32_t>(C / 8)), make_fastdiv(static_cast<uint32_t>(Wo * (C / 8))),        \
       make_fastdiv(static_cast<uint32_t>(Ho)), static_cast<uint32_t>(total))
-#define CXN_POOL_FWD(SSV, KSV)                   \
-  do {                                           \
-    if (nn) CXN_POOL_FWD_T(SSV, KSV, true);      \
-    else CXN_POOL_FWD_T(SSV, KSV, false);        \
-  } while (0)
+#define CXN_POOL_FWD(SSV, KSV) with_flag(nn, [&](auto nnv) { CXN_POOL_FWD_T(SSV, KSV, decltype(nnv)::value); })
     const int sq = KH == KW ? KH : 0;
     if (S == 1 && sq == 3 && mode == 0 && P <= 2 && pool_strips) {
       constexpr int R = 4;
       const int HS = (Ho + R - 1) / R;
       const long tot = static_cast<long>(N) * HS * Wo * (C / 8);
-      if (nn)
-        CXN_LAUNCH((pool_fwd_s1k3<R, true>), cdiv(tot, NT), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, (uint8_t *)arg,
-                   H, W, C, Ho, Wo, P, relu, make_fastdiv(static_cast<uint32_t>(C / 8)),
+      with_flag(nn, [&](auto nnv) {
+        CXN_LAUNCH((pool_fwd_s1k3<R, decltype(nnv)::value>), cdiv(tot, NT), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y,
+                   (uint8_t *)arg, H, W, C, Ho, Wo, P, relu, make_fastdiv(static_cast<uint32_t>(C / 8)),
                    make_fastdiv(static_cast<uint32_t>(Wo * (C / 8))), make_fastdiv(static_cast<uint32_t>(HS)),
                    static_cast<uint32_t>(tot));
-      else
-        CXN_LAUNCH((pool_fwd_s1k3<R, false>), cdiv(tot, NT), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, (uint8_t *)arg,
-                   H, W, C, Ho, Wo, P, relu, make_fastdiv(static_cast<uint32_t>(C / 8)),
-                   make_fastdiv(static_cast<uint32_t>(Wo * (C / 8))), make_fastdiv(static_cast<uint32_t>(HS)),
-                   static_cast<uint32_t>(tot));
+      });
     } else if (S == 2 && sq == 3) CXN_POOL_FWD(2, 3);
     else if (S == 1 && sq == 3) CXN_POOL_FWD(1, 3);
     else if (S == 2 && sq == 2) CXN_POOL_FWD(2, 2);
@@ -2548,16 +2550,10 @@ CXN_API int cxn_lrn_fwd(const void *x, void *y, long npix, int C, int nsize, flo
     const long ngroups = (waves + NT / 64 - 1) / (NT / 64);
     const int blocks = static_cast<int>(std::min<long>(ngroups, 4096));
     const float sa = alpha / nsize;
-#define CXN_LF(HV) CXN_LAUNCH((lrn_fwd_shfl<HV>), blocks, NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, npix, C, sa, beta, \
-                              knorm, ngroups)
-    switch (nsize / 2) {
-      case 0: CXN_LF(0); break;
-      case 1: CXN_LF(1); break;
-      case 2: CXN_LF(2); break;
-      case 3: CXN_LF(3); break;
-      default: CXN_LF(4); break;
-    }
-#undef CXN_LF
+    with_half(nsize / 2, [&](auto hv) {
+      CXN_LAUNCH((lrn_fwd_shfl<decltype(hv)::value>), blocks, NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, npix, C, sa,
+                 beta, knorm, ngroups);
+    });
     RET;
   }
   CXN_LAUNCH((lrn_fwd), nblocks(npix * C / 8), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, npix, C, nsize / 2, alpha / nsize,
@@ -2576,19 +2572,12 @@ CXN_API int cxn_pool_lrn_fwd(const void *x, void *P, void *arg, void *Y, int N, 
   const float sa = alpha / nsize;
   // relu bit 2 (4): the input is a relu output (>= 0): the integer-key max (pool_lrn_fwd NN)
   const bool nn = (relu & 4) != 0 && (relu & 1) == 0;
-#define CXN_PLF(HV)                                                                                            \
-  if (nn) CXN_LAUNCH((pool_lrn_fwd<HV, true>), blocks, NT, 0, S_, (const bf16_t *)x, (bf16_t *)P, (uint8_t *)arg, \
-                     (bf16_t *)Y, N, Hin, Win, C, Ho, Wo, relu, sa, beta, knorm);                                    \
-  else CXN_LAUNCH((pool_lrn_fwd<HV, false>), blocks, NT, 0, S_, (const bf16_t *)x, (bf16_t *)P, (uint8_t *)arg,  \
-                  (bf16_t *)Y, N, Hin, Win, C, Ho, Wo, relu, sa, beta, knorm)
-  switch (half) {
-    case 0: CXN_PLF(0); break;
-    case 1: CXN_PLF(1); break;
-    case 2: CXN_PLF(2); break;
-    case 3: CXN_PLF(3); break;
-    default: CXN_PLF(4); break;
-  }
-#undef CXN_PLF
+  with_half(half, [&](auto hv) {
+    with_flag(nn, [&](auto nnv) {
+      CXN_LAUNCH((pool_lrn_fwd<decltype(hv)::value, decltype(nnv)::value>), blocks, NT, 0, S_, (const bf16_t *)x,
+                 (bf16_t *)P, (uint8_t *)arg, (bf16_t *)Y, N, Hin, Win, C, Ho, Wo, relu, sa, beta, knorm);
+    });
+  });
   RET;
 }
 // dbias_part: fp32 [blocks][C] per-block partial sums of the masked pooled gradient (null: no
@@ -2625,17 +2614,10 @@ CXN_API int cxn_lrn_pool_bwd(const void *P, const void *dY, const void *arg, voi
   if (dbias != nullptr && (part == nullptr || part_rows < blocks)) return -4;
   // (the bias partials reuse the window buffer: at least NT x 9 floats)
   const size_t lds = std::max(static_cast<size_t>((R + 1) * row_bytes), static_cast<size_t>(NT * 9 * 4));
-#define CXN_PLB(HV) CXN_LAUNCH((lrn_pool_bwd<HV>), blocks, NT, lds, S_, (const bf16_t *)P, (const bf16_t *)dY,        \
-                               (const uint8_t *)arg, (bf16_t *)dx, Hin, Win, C, Ho, Wo, HC, WC, R, nband, relu_bit, sa, \
-                               beta, knorm, part)
-  switch (half) {
-    case 0: CXN_PLB(0); break;
-    case 1: CXN_PLB(1); break;
-    case 2: CXN_PLB(2); break;
-    case 3: CXN_PLB(3); break;
-    default: CXN_PLB(4); break;
-  }
-#undef CXN_PLB
+  with_half(half, [&](auto hv) {
+    CXN_LAUNCH((lrn_pool_bwd<decltype(hv)::value>), blocks, NT, lds, S_, (const bf16_t *)P, (const bf16_t *)dY,
+               (const uint8_t *)arg, (bf16_t *)dx, Hin, Win, C, Ho, Wo, HC, WC, R, nband, relu_bit, sa, beta, knorm, part);
+  });
   if (part != nullptr) {
     const int chunk = det ? blocks : 32;  // 4 rows per thread: latency-bound otherwise
     CXN_LAUNCH((part_rows_colsum), dim3((C + 31) / 32, (blocks + chunk - 1) / chunk), NT, 0, S_, part, blocks, C,
@@ -2658,16 +2640,10 @@ CXN_API int cxn_lrn_bwd_db(const void *x, const void *dy, void *dx, long npix, i
   if (part != nullptr && part_floats < 4096L * C) part = nullptr;
   const int blocks = static_cast<int>(std::min<long>(ngroups, part != nullptr ? 4096 : 1024));
   const float sa = alpha / nsize;
-#define CXN_LDB(HV) CXN_LAUNCH((lrn_bwd_db<HV>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, \
-                               npix, C, sa, beta, knorm, mask_relu, ngroups, db, part)
-  switch (half) {
-    case 0: CXN_LDB(0); break;
-    case 1: CXN_LDB(1); break;
-    case 2: CXN_LDB(2); break;
-    case 3: CXN_LDB(3); break;
-    default: CXN_LDB(4); break;
-  }
-#undef CXN_LDB
+  with_half(half, [&](auto hv) {
+    CXN_LAUNCH((lrn_bwd_db<decltype(hv)::value>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx,
+               npix, C, sa, beta, knorm, mask_relu, ngroups, db, part);
+  });
   if (part != nullptr)
     CXN_LAUNCH((part_rows_colsum), dim3((C + 31) / 32, (blocks + 31) / 32), NT, 0, S_, part, blocks, C, db, 32);
   RET;
@@ -2681,13 +2657,10 @@ CXN_API int cxn_lrn_bwd(const void *x, const void *dy, void *dx, long npix, int 
     const long waves = (npix + 64 / tpp - 1) / (64 / tpp);
     const int blocks = static_cast<int>((waves + NT / 64 - 1) / (NT / 64));
     const float sa = alpha / nsize;
-    switch (half) {
-      case 0: CXN_LAUNCH((lrn_bwd_shfl<0>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu); break;
-      case 1: CXN_LAUNCH((lrn_bwd_shfl<1>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu); break;
-      case 2: CXN_LAUNCH((lrn_bwd_shfl<2>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu); break;
-      case 3: CXN_LAUNCH((lrn_bwd_shfl<3>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu); break;
-      default: CXN_LAUNCH((lrn_bwd_shfl<4>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy, (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu); break;
-    }
+    with_half(half, [&](auto hv) {
+      CXN_LAUNCH((lrn_bwd_shfl<decltype(hv)::value>), blocks, NT, 0, S_, (const bf16_t *)x, (const bf16_t *)dy,
+                 (bf16_t *)dx, npix, C, sa, beta, knorm, mask_relu);
+    });
     RET;
   }
   if (tpp <= NT && (C + 2 * half) * 3 * 4 * (NT / tpp) <= 48 * 1024) {
@@ -2715,9 +2688,8 @@ CXN_API int cxn_act_bwd(const void *y, const void *dy, void *dx, long n, int kin
 }
 CXN_API int cxn_dropout(const void *x, void *y, long n, unsigned seed, const int *counter, float pkeep,
                         void *stream) {
-  const double t = static_cast<double>(pkeep) * 4294967296.0;
-  const uint32_t thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t);
-  CXN_LAUNCH((dropout_apply), nblocks(n / 8 + 1), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, n, seed, counter, thresh, 1.0f / pkeep);
+  CXN_LAUNCH((dropout_apply), nblocks(n / 8 + 1), NT, 0, S_, (const bf16_t *)x, (bf16_t *)y, n, seed, counter,
+             dropout_thresh(pkeep), 1.0f / pkeep);
   RET;
 }
 
@@ -2852,10 +2824,8 @@ CXN_API int cxn_splitk_finalize_dropout(const float *ws, int nsplit, long slab, 
                                         void *stream) {
   if (cols % 8 || static_cast<double>(rows) * cols >= 4294967296.0) return -2;
   dim3 grid(cdiv(cols / 8, NT), static_cast<unsigned>(rows));
-  const double t = static_cast<double>(pkeep) * 4294967296.0;  // as cxn_dropout
-  const uint32_t thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t);
   CXN_LAUNCH((splitk_finalize<true>), grid, NT, 0, S_, ws, nsplit, slab, (bf16_t *)out, rows, cols, bias, relu, 0,
-             static_cast<uint32_t>(seed), counter, thresh, 1.f / pkeep);
+             static_cast<uint32_t>(seed), counter, dropout_thresh(pkeep), 1.f / pkeep);
   RET;
 }
 CXN_API int cxn_cast_f32_bf16(const float *x, void *y, long n, void *stream) {

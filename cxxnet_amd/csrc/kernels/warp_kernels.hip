@@ -105,7 +105,6 @@ __global__ void __launch_bounds__(256) image_warp(const uint8_t *__restrict__ sr
 
 }  // namespace
 
-#define S_ static_cast<hipStream_t>(stream)
 
 // src packed RGB regions, table int64 [B][16], wtab int32 [32][32][16] (16-byte aligned) ->
 // out uint8 [r1 - r0][h][w][C] for batch rows r0..r1.  The caller checked the regions against the

@@ -23,7 +23,7 @@ def _ctr(counter):
 
 
 def uniform_ref(n: int, seed: int, device="cpu") -> torch.Tensor:
-    """u01 of layer_kernels.hip: hash(i, seed) * 2^-32 in fp32."""
+    """u01 of layer_kernels.hip: hash_u32(i, seed) (csrc/kernels/common.h) * 2^-32 in fp32."""
     idx = torch.arange(n, dtype=torch.int64, device=device)
     return _hash_u32(idx, seed & 0xFFFFFFFF).to(torch.float32) * 2.3283064365386963e-10
 

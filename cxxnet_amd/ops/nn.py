@@ -523,7 +523,7 @@ def act_backward(kind, y, dy, dx, b=5.0):
 
 # ----------------------------------------------------------------------------- dropout
 def _hash_u32(idx: torch.Tensor, seed: int) -> torch.Tensor:
-    # identical to hash_u32 in nn_kernels.hip, in int64 arithmetic masked to 32 bits
+    # identical to hash_u32 in csrc/kernels/common.h, in int64 arithmetic masked to 32 bits
     M = 0xFFFFFFFF
     x = idx ^ ((seed * 0x9E3779B9) & M)
     x = x ^ (x >> 16); x = (x * 0x7FEB352D) & M
