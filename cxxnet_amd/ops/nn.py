@@ -423,13 +423,18 @@ def pool_backward_tie_all(x, y, dy, dx, KH, KW, S, P, relu=False):
 
 
 # ----------------------------------------------------------------------------- LRN
-def _lrn_norm(x, nsize, alpha, knorm):
-    C = x.shape[-1]
+def _lrn_window_sum(v, nsize):
+    """Sum over channels c - h .. c + h (h = nsize // 2) clipped to [0, C): the window of the
+    kernels (nn_kernels.hip) and of the reference's chpool, which centres 2 h + 1 channels on c;
+    for an even local_size that is one channel more than nsize."""
+    C = v.shape[-1]
     half = nsize // 2
-    sq = x * x
-    pad = F.pad(sq, (half, half))
-    s = sum(pad[..., i:i + C] for i in range(nsize))
-    return knorm + alpha / nsize * s
+    pad = F.pad(v, (half, half))
+    return sum(pad[..., i:i + C] for i in range(2 * half + 1))
+
+
+def _lrn_norm(x, nsize, alpha, knorm):
+    return knorm + alpha / nsize * _lrn_window_sum(x * x, nsize)
 
 
 def lrn_forward(x, y, nsize, alpha, beta, knorm):
@@ -465,10 +470,7 @@ def lrn_backward(x, dy, dx, nsize, alpha, beta, knorm, mask_relu=False):
     if not _native_t(x):
         norm = _lrn_norm(x, nsize, alpha, knorm)
         t = dy * x * norm.pow(-beta - 1)
-        C = x.shape[-1]
-        half = nsize // 2
-        tp = F.pad(t, (half, half))
-        s = sum(tp[..., i:i + C] for i in range(nsize))
+        s = _lrn_window_sum(t, nsize)
         g = dy * norm.pow(-beta) - 2 * beta * alpha / nsize * x * s
         if mask_relu:
             g = torch.where(x > 0, g, torch.zeros_like(g))
