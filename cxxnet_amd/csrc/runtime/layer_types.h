@@ -41,6 +41,7 @@ enum : int {
   kFixConnect = 31,
   // extensions without a reference counterpart: ids the reference enumeration leaves unused
   kBatchNormMA = 40,
+  kAdd = 41,
   kPairTestGap = 1024,
 };
 
@@ -59,7 +60,7 @@ inline int GetLayerType(const std::string &t) {
       {"insanity", kInsanity}, {"insanity_max_pooling", kInsanityPooling},
       {"l2_loss", kL2Loss}, {"multi_logistic", kMultiLogistic},
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
-      {"batch_norm_ma", kBatchNormMA},
+      {"batch_norm_ma", kBatchNormMA}, {"add", kAdd},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,9 +1,9 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
-insanity, insanity_max_pooling, fixconn, pairtest -- and the extension batch_norm_ma.
+insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma and add.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
-csrc/kernels/bn_ma_kernels.hip, concat / split /
+csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, concat / split /
 bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
@@ -358,6 +358,58 @@ class BatchNormMALayer(Layer):
         return self.loaded
 
 
+class AddLayer(Layer):
+    """`add` (type id 41) -- an extension, no reference counterpart: the element-wise sum of 2-4
+    nodes of one shape, the join of a residual block.  acc = x0 + x1 (+ x2 + x3) in fp32 in input
+    order; y = acc, or relu(acc) with add_relu = 1, rounded once to the node's dtype.  Backward
+    hands the output node's gradient g to every input's gdst: g itself, or with add_relu = 1 g
+    where the stored y was > 0 and exactly 0 elsewhere.  The output node holds g by then, so the
+    sign of y is kept as one bit per element, written by the training forward (L.AddState).  The
+    layer only reads its inputs in forward, so it may consume zero-copy split outputs
+    (NeuralNet._fuse_split).  No parameters and no state: the checkpoint holds nothing for it."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "add"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.relu = False
+        self._st = None
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "add_relu":
+            _check(val.strip() in ("0", "1"), "AddLayer: add_relu must be 0 or 1")
+            self.relu = val.strip() == "1"
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(2 <= len(nodes_in) <= 4 and len(nodes_out) == 1, "AddLayer: only support n-1 connection, n = 2..4")
+        out = nodes_out[0]
+        _check(all(n is not out for n in nodes_in), "AddLayer: the output node must differ from every input")
+        _check(len({id(n) for n in nodes_in}) == len(nodes_in), "AddLayer: the input nodes must be distinct")
+        for n in nodes_in:
+            _check(n.shape == nodes_in[0].shape, "AddLayer: input shapes do not match")
+            _check(n.cp == n.shape[1], "AddLayer: padded-channel inputs are not supported")
+        out.set_shape(*nodes_in[0].shape)
+        b, c, h, w = out.shape
+        self.max_numel = b * c * h * w
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        st = None
+        if self.relu and is_train:
+            if self._st is None:  # once, for the largest batch
+                self._st = L.AddState(self.max_numel, nodes_out[0].data.device, self.ctx.is_gpu)
+            st = self._st
+        L.add_forward([n.data for n in nodes_in], nodes_out[0].data, self.relu, st)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if not prop_grad:
+            return
+        _check(not self.relu or self._st is not None, "AddLayer: backprop without a training forward")
+        L.add_backward(nodes_out[0].data, [n.gdst for n in nodes_in], self._st if self.relu else None)
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -668,6 +720,7 @@ def _register():
     register(28, lambda ctx: ConcatLayer(ctx, 1))
     register(30, BatchNormLayer)
     register(40, BatchNormMALayer)
+    register(41, AddLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

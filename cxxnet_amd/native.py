@@ -95,6 +95,9 @@ _SIGS = {
     "cxn_bn_ma_fwd_train": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _F, _F, _P],
     "cxn_bn_ma_fwd_infer": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "cxn_bn_ma_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    # add (csrc/kernels/add_kernels.hip)
+    "cxn_add_fwd": [_P, _P, _P, _P, _I, _P, _P, _L, _I, _P],
+    "cxn_add_bwd": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
     "cxn_rand_fill": [_P, _L, _U, _I, _F, _F, _P],
     "cxn_prelu": [_P, _P, _P, _P, _L, _I, _U, _P, _F, _I, _P],
     "cxn_insanity": [_P, _P, _P, _P, _L, _F, _F, _I, _U, _P, _I, _P],

@@ -35,11 +35,12 @@ from ..io.warp_stage import WarpImages
 K_CONV, K_FULLC, K_RELU, K_MAXPOOL, K_DROPOUT = 10, 1, 3, 11, 8
 K_SPLIT, K_CONCAT, K_CHCONCAT, K_SUMPOOL, K_AVGPOOL, K_LRN = 23, 18, 28, 12, 13, 15
 K_RELU_MAXPOOL = 21
+K_ADD = 41  # extension (layers/extra.py AddLayer)
 # queued bias-gradient bytes (dy read by the column sums) that trigger a side-stream launch
 _BIAS_FLUSH_BYTES = int(float(os.environ.get("CXXNET_BIAS_FLUSH_MB", "16")) * (1 << 20))
 # layers that only READ their input node in forward and write the input gradient through
 # Node.gdst: they may consume a zero-copy split output
-_SPLIT_SAFE = (K_CONV, K_FULLC, K_MAXPOOL, K_SUMPOOL, K_AVGPOOL, K_LRN)
+_SPLIT_SAFE = (K_CONV, K_FULLC, K_MAXPOOL, K_SUMPOOL, K_AVGPOOL, K_LRN, K_ADD)
 
 
 class Connection:
@@ -214,6 +215,8 @@ class NeuralNet:
             ins = conn.nodes_in
             if t == K_RELU or (t in (K_CONV, K_FULLC) and getattr(lay, "fuse_relu", False)):
                 ok = True
+            elif t == K_ADD:  # relu(sum) with add_relu = 1; a plain sum of non-negative nodes is not claimed
+                ok = bool(lay.relu)
             elif t in (K_MAXPOOL, K_RELU_MAXPOOL):
                 ok = t == K_RELU_MAXPOOL or bool(getattr(lay, "relu", False)) or all(id(n) in nn for n in ins)
                 lay.input_nonneg = all(id(n) in nn for n in ins)
@@ -415,7 +418,10 @@ class NeuralNet:
         """Zero-copy split: when the split is its input's only reader and every output feeds
         exactly one read-only-in-forward layer, the outputs alias the input buffer and each
         consumer's data-gradient goes to the output node's private grad buffer (summed by the
-        split's backward).  Saves one full activation copy per branch per step."""
+        split's backward).  Saves one full activation copy per branch per step.  An `add` counts
+        as such a layer although it has several inputs: it reads all of them in forward only and
+        writes their gradients through gdst, so the identity branch of a residual block aliases
+        the block input."""
         self.split_alias = {}
         for i, conn in enumerate(self.connections):
             if conn.type != K_SPLIT or conn.shared or len(conn.nodes_in) != 1:
@@ -431,7 +437,8 @@ class NeuralNet:
                     break
                 j = cons[0][0]
                 cj = self.connections[j]
-                if j == 0 or cj.type not in _SPLIT_SAFE or len(cj.nodes_in) != 1 or cj.layer.grad_mask_relu:
+                if (j == 0 or cj.type not in _SPLIT_SAFE or (len(cj.nodes_in) != 1 and cj.type != K_ADD)
+                        or cj.layer.grad_mask_relu):
                     ok = False
                     break
             if not ok:

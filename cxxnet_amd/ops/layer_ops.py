@@ -204,6 +204,66 @@ def bn_ma_backward(g2d, x2d, dx2d, slope, gslope, gbias, st: BNMAState, prop_gra
                  "bn_ma_bwd")
 
 
+# ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
+class AddState:
+    """The relu mask of an `add` layer with add_relu = 1, sized once for the layer's largest
+    batch.  HIP path: ceil(n / 8) bytes, bit j of byte r = "element 8 r + j of the stored y is
+    > 0" (csrc/kernels/add_kernels.hip).  Torch path (CPU, precision = fp32): n bools."""
+
+    def __init__(self, max_numel, device, packed):
+        self.packed = bool(packed)
+        if self.packed:
+            self.mask = torch.zeros((int(max_numel) + 7) // 8, dtype=torch.uint8, device=device)
+        else:
+            self.mask = torch.zeros(int(max_numel), dtype=torch.bool, device=device)
+
+
+def _flat_bf16(*ts):
+    for t in ts:
+        if not (t.is_contiguous() and t.dtype == torch.bfloat16):
+            raise ValueError("add: contiguous bf16 tensors expected")
+
+
+def add_forward(xs, y, relu: bool, st: AddState = None):
+    """y = x0 + x1 (+ x2 + x3), fp32 accumulation in input order, then relu when `relu`, one
+    rounding to y's dtype.  st (training forward with relu): receives the mask "stored y > 0".
+    y must not alias an input."""
+    n = y.numel()
+    if not 2 <= len(xs) <= 4 or any(x.numel() != n for x in xs):
+        raise ValueError("add: 2 to 4 inputs of the output's size expected")
+    if not _native_t(y):
+        acc = xs[0].float()
+        for x in xs[1:]:
+            acc = acc + x.float()
+        if relu:
+            acc = torch.where(acc > 0, acc, torch.zeros_like(acc))
+        y.copy_(acc)
+        if st is not None:
+            torch.gt(y.reshape(-1), 0, out=st.mask[:n])
+        return
+    _flat_bf16(y, *xs)
+    ptr = [x.data_ptr() for x in xs] + [None] * (4 - len(xs))
+    native.check(_k().cxn_add_fwd(*ptr, len(xs), y.data_ptr(), st.mask.data_ptr() if st is not None else None, n,
+                                  int(bool(relu)), _stream()), "add_fwd")
+
+
+def add_backward(g, dsts, st: AddState = None):
+    """Every dst = g where the forward's stored y was > 0 and exactly 0 elsewhere (st: the
+    forward's mask); st None: every dst = g.  No dst may alias g."""
+    n = g.numel()
+    if not 1 <= len(dsts) <= 4 or any(d.numel() != n for d in dsts):
+        raise ValueError("add: 1 to 4 destinations of the gradient's size expected")
+    if not _native_t(g):
+        v = g if st is None else torch.where(st.mask[:n].view(g.shape), g, torch.zeros_like(g))
+        for d in dsts:
+            d.copy_(v)
+        return
+    _flat_bf16(g, *dsts)
+    ptr = [d.data_ptr() for d in dsts] + [None] * (4 - len(dsts))
+    native.check(_k().cxn_add_bwd(g.data_ptr(), st.mask.data_ptr() if st is not None else None, *ptr, len(dsts), n,
+                                  _stream()), "add_bwd")
+
+
 # ----------------------------------------------------------------------------- prelu
 def _prelu_mask_ref(x2d, slope, seed, counter, rnd):
     rows, C = x2d.shape
