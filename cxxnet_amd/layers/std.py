@@ -370,6 +370,11 @@ class ConvolutionLayer(Layer):
             _check(lp.num_input_channel == c, "ConvolutionLayer: number of input channels is not consistent")
         G = lp.num_group
         _check(c % G == 0 and lp.num_channel % G == 0, "ConvolutionLayer: channels must divide ngroup")
+        # depthwise (ngroup = the input channel count): every group is one physical channel, so
+        # a channel-padded input cannot be regrouped
+        _check(not (G > 1 and G == c) or x.cp == c,
+               "ConvolutionLayer: a depthwise conv (ngroup = input channels = %d) needs an unpadded input, got %d "
+               "physical channels" % (c, x.cp))
         Ho, Wo = conv_out_size(h, w, lp.kernel_height, lp.kernel_width, lp.stride, lp.pad_y, lp.pad_x)
         nodes_out[0].set_shape(b, lp.num_channel, Ho, Wo)
         self.cin_phys = x.cp

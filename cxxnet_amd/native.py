@@ -98,6 +98,10 @@ _SIGS = {
     # add (csrc/kernels/add_kernels.hip)
     "cxn_add_fwd": [_P, _P, _P, _P, _I, _P, _P, _L, _I, _P],
     "cxn_add_bwd": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
+    # depthwise conv (csrc/kernels/dwconv_kernels.hip)
+    "cxn_dwconv_fwd": [_P, _L, _P, _P, _P, _L] + [_I] * 12 + [_P],
+    "cxn_dwconv_bwd_data": [_P, _L, _P, _P, _L] + [_I] * 12 + [_P],
+    "cxn_dwconv_bwd_weight": [_P, _L, _P, _L, _P, _P, _P, _L] + [_I] * 11 + [_P],
     "cxn_rand_fill": [_P, _L, _U, _I, _F, _F, _P],
     "cxn_prelu": [_P, _P, _P, _P, _L, _I, _U, _P, _F, _I, _P],
     "cxn_insanity": [_P, _P, _P, _P, _L, _F, _F, _I, _U, _P, _I, _P],

@@ -690,6 +690,90 @@ def conv_forward_fewc(x, w, bias, y, g: ConvGeom, relu=False) -> bool:
     return served(rc, "conv_fewc_fwd")
 
 
+# ------------------------------------------------------------------------------------ depthwise
+# Depthwise convolution (one input channel per group) on the direct kernels of
+# csrc/kernels/dwconv_kernels.hip: a memory-bound stencil, nothing for the MFMA GEMMs to reduce.
+# CXXNET_DW=0 switches the path off (such a layer then raises as a GEMM geometry does).
+_DW = os.environ.get("CXXNET_DW", "1") != "0"
+DW_SERVED = ("groups == C == Cout (channel multiplier 1), C % 8 == 0, KH == KW in {3, 5}, stride in {1, 2}, "
+             "pad_y and pad_x in [0, K)")
+
+
+def is_depthwise(g: ConvGeom) -> bool:
+    """The geometry belongs to the depthwise kernels, not to the GEMMs: groups == C, so every
+    group reads one input channel (groups == C == Cout is the form served; a channel multiplier
+    > 1 is declined by dwconv_served).  A pure function of the geometry."""
+    return g.groups > 1 and g.groups == g.C and g.Cout % g.groups == 0
+
+
+def dwconv_served(g: ConvGeom) -> bool:
+    """The shape rule of cxn_dwconv_* (serves() in dwconv_kernels.hip), without launching."""
+    return (is_depthwise(g) and g.Cout == g.C and g.C % 8 == 0 and g.KH == g.KW and g.KH in (3, 5)
+            and g.stride in (1, 2) and 0 <= g.pad_y < g.KH and 0 <= g.pad_x < g.KW
+            and g.H + 2 * g.pad_y >= g.KH and g.W + 2 * g.pad_x >= g.KW)
+
+
+def dwconv_wgrad_partials(g: ConvGeom):
+    """(P, workspace floats) of cxn_dwconv_bwd_weight: the launcher's own formula.  A lane owns 8
+    channels; a block is GX = min(C / 8, 256) group lanes x RL = 256 // GX item lanes; an item is
+    a run of 2 output pixels of one row; each block takes ipb consecutive
+    items -- an even share of at most 512 // ny slabs, and at least 4 per item lane -- and writes
+    one slab of C (K K + 1) floats (dw, then db)."""
+    G = g.C // 8
+    GX = min(G, 256)
+    RL = 256 // GX
+    ny = _cdiv(G, GX)
+    R = g.N * g.Ho * _cdiv(g.Wo, 2)
+    ipb = max(_cdiv(R, max(512 // ny, 1)), RL * 4)
+    P = _cdiv(R, ipb)
+    return P, P * g.C * (g.KH * g.KW + 1)
+
+
+def _dw_check(g: ConvGeom, what: str, *acts):
+    if not dwconv_served(g):
+        raise ValueError(f"{what}: depthwise geometry {g} is not served by the direct kernels (served: {DW_SERVED})")
+    for t in acts:
+        if t.stride(-1) != 1 or _pix(t) % 8 or t.data_ptr() % 16:
+            raise ValueError(f"{what}: depthwise geometry {g}: an activation operand is not 16-byte aligned "
+                             f"8-channel vectors (pixel stride {_pix(t)})")
+
+
+def _dw_args(g: ConvGeom):
+    return (g.N, g.H, g.W, g.C, g.Cout, g.groups, g.KH, g.KW, g.stride, g.pad_y, g.pad_x)
+
+
+def _dw_done(rc, g: ConvGeom, what: str):
+    if not served(rc, what):
+        raise ValueError(f"{what}: depthwise geometry {g} declined by the kernel (served: {DW_SERVED})")
+
+
+def dwconv_forward(x, w, bias, y, g: ConvGeom, relu=False):
+    """y = [relu](dwconv(x, w) + bias) on cxn_dwconv_fwd; ValueError for a geometry not served."""
+    _dw_check(g, "conv", x, y)
+    _dw_done(native.kernels().cxn_dwconv_fwd(x.data_ptr(), _pix(x), w.data_ptr(),
+                                             bias.data_ptr() if bias is not None else None, y.data_ptr(), _pix(y),
+                                             *_dw_args(g), int(relu), _stream()), g, "dwconv_fwd")
+
+
+def dwconv_backward_data(dy, w, dx, g: ConvGeom, mask_relu=False):
+    """dx = dwconv_transpose(dy, w), every element of dx written (relu'-masked when mask_relu: dx
+    holds relu(z) on entry) on cxn_dwconv_bwd_data, from w itself: no flipped copy."""
+    _dw_check(g, "conv dgrad", dy, dx)
+    _dw_done(native.kernels().cxn_dwconv_bwd_data(dy.data_ptr(), _pix(dy), w.data_ptr(), dx.data_ptr(), _pix(dx),
+                                                  *_dw_args(g), int(mask_relu), _stream()), g, "dwconv_bwd_data")
+
+
+def dwconv_backward_weight(x, dy, dw, g: ConvGeom, db=None):
+    """dw += the depthwise weight gradient, db (optional) += the bias gradient in the same pass, on
+    cxn_dwconv_bwd_weight: fixed-order partial sums, bitwise reproducible."""
+    _dw_check(g, "conv weight-grad", x, dy)
+    _, need = dwconv_wgrad_partials(g)
+    ws = workspace("dwconv_wgrad", need, dw.device, 1 << 16)
+    _dw_done(native.kernels().cxn_dwconv_bwd_weight(x.data_ptr(), _pix(x), dy.data_ptr(), _pix(dy), dw.data_ptr(),
+                                                    db.data_ptr() if db is not None else None, ws.data_ptr(),
+                                                    ws.numel(), *_dw_args(g), _stream()), g, "dwconv_bwd_weight")
+
+
 def _fwd_operands(x, w, g: ConvGeom):
     """The forward implicit GEMM: A = the weights ([cg_out][kdim] per group), B = the im2col gather
     of x.  B's C is the input's pixel stride: a channel slice of a wider buffer (sibling outputs,
@@ -747,6 +831,8 @@ def conv_forward(x, w, bias, y, g: ConvGeom, relu=False):
             out = out.clamp_min(0)
         y.copy_(out.permute(0, 2, 3, 1))
         return
+    if _DW and is_depthwise(g):
+        return dwconv_forward(x, w, bias, y, g, relu=relu)
     cg = g.cg_in
     va = 8 if cg % 8 == 0 else 4
     if g.C == 4 and conv_rowrun_fwd2(x, w, bias, y, g, relu):  # padded 4-channel first layers (GoogLeNet conv1)
@@ -835,7 +921,8 @@ def conv_forward_split(x, w, bias, y, y2, split, g: ConvGeom, relu=False):
 def conv_weight_flip_multi(items):
     """wt = w with (Cout, Cin) swapped and the taps reversed (the data-gradient GEMM's weight
     operand), for every (w, wt, geometry) of `items` in one launch."""
-    items = [it for it in items if _native_t(it[0])]
+    # (a depthwise data gradient reads w itself: nothing to flip)
+    items = [it for it in items if _native_t(it[0]) and not (_DW and is_depthwise(it[2]))]
     if not items:
         return
     n = len(items)
@@ -862,6 +949,9 @@ def conv_backward_data(dy, w, dx, g: ConvGeom, wt_buf=None, mask_relu=False, wt_
         if mask_relu:
             out = out * (dx > 0).to(out.dtype)
         dx.copy_(out)
+        return False
+    if _DW and is_depthwise(g):  # (no dbias epilogue: the caller sums it itself)
+        dwconv_backward_data(dy, w, dx, g, mask_relu=mask_relu)
         return False
     cg_in = g.cg_in
     if g.cg_out % 8:
@@ -1055,6 +1145,9 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
                                          padding=(g.pad_y, g.pad_x), groups=g.groups)
         dw.add_(gw.permute(0, 2, 3, 1))
         return
+    if _DW and is_depthwise(g):
+        dwconv_backward_weight(x, dy, dw, g, db=db)
+        return db is not None
     cg = g.cg_in
     va = 8 if cg % 8 == 0 else 4
     kd = g.kdim
