@@ -42,6 +42,7 @@ enum : int {
   // extensions without a reference counterpart: ids the reference enumeration leaves unused
   kBatchNormMA = 40,
   kAdd = 41,
+  kChScale = 42,
   kPairTestGap = 1024,
 };
 
@@ -60,7 +61,7 @@ inline int GetLayerType(const std::string &t) {
       {"insanity", kInsanity}, {"insanity_max_pooling", kInsanityPooling},
       {"l2_loss", kL2Loss}, {"multi_logistic", kMultiLogistic},
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
-      {"batch_norm_ma", kBatchNormMA}, {"add", kAdd},
+      {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,10 +1,11 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
-insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma and add.
+insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add and
+ch_scale.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
-csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, concat / split /
-bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
+csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, ch_scale in
+csrc/kernels/se_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
 from __future__ import annotations
@@ -410,6 +411,52 @@ class AddLayer(Layer):
         L.add_backward(nodes_out[0].data, [n.gdst for n in nodes_in], self._st if self.relu else None)
 
 
+class ChScaleLayer(Layer):
+    """`ch_scale` (type id 42) -- an extension, no reference counterpart: the product of a
+    feature map x (B,C,H,W) with a per-sample, per-channel gate s of B C elements, a matrix node
+    (B,1,1,C) or a node (B,C,1,1) (both [b][c] in memory), the excitation of a
+    squeeze-and-excitation block: `layer[x,s->y] = ch_scale`.  y[b,h,w,c] = x[b,h,w,c] s[b,c] in
+    fp32, rounded once to the node's dtype, the same for is_train true and false.  Backward, with
+    g the gradient held by the output node: dx = g s into x.gdst and ds[b,c] = sum over the map of
+    g x (fp32, a fixed order, one rounding) into s.gdst; x.gdst may be x.data and s.gdst normally
+    is s.data, which the kernels allow.  The layer only reads x.data, in both directions, so x may
+    be a zero-copy split output (NeuralNet._fuse_split); s may not.  No parameters and no state:
+    the checkpoint holds nothing for it."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "ch_scale"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self._st = None
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 2 and len(nodes_out) == 1, "ChScaleLayer: only support 2-1 connection")
+        x, s = nodes_in
+        out = nodes_out[0]
+        _check(x is not s, "ChScaleLayer: the input nodes must be distinct")
+        _check(out is not x and out is not s, "ChScaleLayer: the output node must differ from every input")
+        b, c, h, w = x.shape
+        _check(s.shape in ((b, 1, 1, c), (b, c, 1, 1)),
+               "ChScaleLayer: the gate must be a (batch,1,1,C) or (batch,C,1,1) node with the map's batch and channels")
+        for n in nodes_in:
+            _check(n.cp == n.shape[1], "ChScaleLayer: padded-channel inputs are not supported")
+        out.set_shape(b, c, h, w)
+        self.max_batch, self.hw, self.channel = b, h * w, c
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        L.ch_scale_forward(nodes_in[0].data, nodes_in[1].data, nodes_out[0].data)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if not prop_grad:
+            return
+        x, s = nodes_in
+        if self._st is None:  # once, for the largest batch
+            self._st = L.ChScaleState(self.max_batch, self.hw, self.channel, x.data.device, self.ctx.is_gpu)
+        L.ch_scale_backward(nodes_out[0].data, x.data, s.data, x.gdst, s.gdst, self._st)
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -721,6 +768,7 @@ def _register():
     register(30, BatchNormLayer)
     register(40, BatchNormMALayer)
     register(41, AddLayer)
+    register(42, ChScaleLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -98,6 +98,12 @@ _SIGS = {
     # add (csrc/kernels/add_kernels.hip)
     "cxn_add_fwd": [_P, _P, _P, _P, _I, _P, _P, _L, _I, _P],
     "cxn_add_bwd": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
+    # ch_scale and global sum / avg pooling (csrc/kernels/se_kernels.hip)
+    "cxn_se_parts": [_L, _L, _I],
+    "cxn_se_ws_floats": [_L, _L, _I],
+    "cxn_ch_scale_fwd": [_P, _P, _P, _L, _L, _I, _P],
+    "cxn_ch_scale_bwd": [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P],
+    "cxn_global_pool_fwd": [_P, _P, _P, _L, _L, _L, _I, _F, _P],
     # depthwise conv (csrc/kernels/dwconv_kernels.hip)
     "cxn_dwconv_fwd": [_P, _L, _P, _P, _P, _L] + [_I] * 12 + [_P],
     "cxn_dwconv_bwd_data": [_P, _L, _P, _P, _L] + [_I] * 12 + [_P],
@@ -162,6 +168,7 @@ _SIGS = {
 }
 _RESTYPE = {"cxn_gemm_sgd_stream_calls": ctypes.c_long, "cxn_rec_end": ctypes.c_void_p, "cxn_rec_free": None,
             "cxn_conv_wgrad_direct": ctypes.c_long, "cxn_bn_ma_ws_floats": ctypes.c_long,
+            "cxn_se_ws_floats": ctypes.c_long,
             "cxn_conv_wgrad_rowrun": ctypes.c_long,
             "cxn_conv_direct": ctypes.c_long}
 

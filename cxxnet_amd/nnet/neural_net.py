@@ -36,11 +36,12 @@ K_CONV, K_FULLC, K_RELU, K_MAXPOOL, K_DROPOUT = 10, 1, 3, 11, 8
 K_SPLIT, K_CONCAT, K_CHCONCAT, K_SUMPOOL, K_AVGPOOL, K_LRN = 23, 18, 28, 12, 13, 15
 K_RELU_MAXPOOL = 21
 K_ADD = 41  # extension (layers/extra.py AddLayer)
+K_CH_SCALE = 42  # extension (layers/extra.py ChScaleLayer)
 # queued bias-gradient bytes (dy read by the column sums) that trigger a side-stream launch
 _BIAS_FLUSH_BYTES = int(float(os.environ.get("CXXNET_BIAS_FLUSH_MB", "16")) * (1 << 20))
 # layers that only READ their input node in forward and write the input gradient through
 # Node.gdst: they may consume a zero-copy split output
-_SPLIT_SAFE = (K_CONV, K_FULLC, K_MAXPOOL, K_SUMPOOL, K_AVGPOOL, K_LRN, K_ADD)
+_SPLIT_SAFE = (K_CONV, K_FULLC, K_MAXPOOL, K_SUMPOOL, K_AVGPOOL, K_LRN, K_ADD, K_CH_SCALE)
 
 
 class Connection:
@@ -421,7 +422,9 @@ class NeuralNet:
         split's backward).  Saves one full activation copy per branch per step.  An `add` counts
         as such a layer although it has several inputs: it reads all of them in forward only and
         writes their gradients through gdst, so the identity branch of a residual block aliases
-        the block input."""
+        the block input.  So does a `ch_scale` for its first input, the feature map, which it only
+        reads (forward and backward; the split's sum overwrites the shared buffer after every
+        consumer's backprop); a split output used as its gate keeps the copying split."""
         self.split_alias = {}
         for i, conn in enumerate(self.connections):
             if conn.type != K_SPLIT or conn.shared or len(conn.nodes_in) != 1:
@@ -437,7 +440,9 @@ class NeuralNet:
                     break
                 j = cons[0][0]
                 cj = self.connections[j]
-                if (j == 0 or cj.type not in _SPLIT_SAFE or (len(cj.nodes_in) != 1 and cj.type != K_ADD)
+                multi_ok = cj.type == K_ADD or (cj.type == K_CH_SCALE and cj.nodes_in[0] is o
+                                                and cj.nodes_in[1] is not o)
+                if (j == 0 or cj.type not in _SPLIT_SAFE or (len(cj.nodes_in) != 1 and not multi_ok)
                         or cj.layer.grad_mask_relu):
                     ok = False
                     break

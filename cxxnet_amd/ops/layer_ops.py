@@ -218,10 +218,10 @@ class AddState:
             self.mask = torch.zeros(int(max_numel), dtype=torch.bool, device=device)
 
 
-def _flat_bf16(*ts):
+def _flat_bf16(*ts, who="add"):
     for t in ts:
         if not (t.is_contiguous() and t.dtype == torch.bfloat16):
-            raise ValueError("add: contiguous bf16 tensors expected")
+            raise ValueError(who + ": contiguous bf16 tensors expected")
 
 
 def add_forward(xs, y, relu: bool, st: AddState = None):
@@ -262,6 +262,64 @@ def add_backward(g, dsts, st: AddState = None):
     ptr = [d.data_ptr() for d in dsts] + [None] * (4 - len(dsts))
     native.check(_k().cxn_add_bwd(g.data_ptr(), st.mask.data_ptr() if st is not None else None, *ptr, len(dsts), n,
                                   _stream()), "add_bwd")
+
+
+# ----------------------------------------------------------------------------- ch_scale (per-sample channel gate)
+def se_parts(B: int, HW: int, C: int) -> int:
+    """Parts the ch_scale backward and the global pooling cut a map of HW pixels into
+    (csrc/kernels/se_kernels.hip): a function of the shape alone.  1: no workspace, one launch."""
+    n = int(_k().cxn_se_parts(int(B), int(HW), int(C)))
+    if n < 1:
+        raise ValueError("se_parts: bad shape (%d, %d, %d)" % (B, HW, C))
+    return n
+
+
+class ChScaleState:
+    """The fp32 partial workspace [part][B C] of a `ch_scale` layer's backward, sized once for
+    every batch up to max_batch (csrc/kernels/se_kernels.hip).  None on the torch path and where
+    one block owns a whole (image, channel group)."""
+
+    def __init__(self, max_batch, HW, C, device, native_path):
+        self.ws = None
+        if native_path:
+            n = int(_k().cxn_se_ws_floats(int(max_batch), int(HW), int(C)))
+            if n > 0:
+                self.ws = torch.zeros(n, dtype=torch.float32, device=device)
+
+
+def _ch_scale_dims(x, s):
+    if x.dim() != 4 or s.numel() != x.shape[0] * x.shape[3]:
+        raise ValueError("ch_scale: x [B][H][W][C] and a gate of B C elements expected")
+    return x.shape[0], x.shape[1] * x.shape[2], x.shape[3]
+
+
+def ch_scale_forward(x, s, y):
+    """y[b,h,w,c] = x[b,h,w,c] s[b,c] in fp32, one rounding to y's dtype.  x, y NHWC; s any
+    contiguous tensor of B C elements in [b][c] order.  y must not alias x or s."""
+    B, HW, C = _ch_scale_dims(x, s)
+    if not _native_t(x):
+        y.copy_(x.float() * s.reshape(B, 1, 1, C).float())
+        return
+    _flat_bf16(x, s, y, who="ch_scale")
+    native.check(_k().cxn_ch_scale_fwd(x.data_ptr(), s.data_ptr(), y.data_ptr(), B, HW, C, _stream()), "ch_scale_fwd")
+
+
+def ch_scale_backward(g, x, s, dx, ds, st: ChScaleState = None):
+    """dx = g s (one rounding) and ds[b,c] = sum over the map of g x, accumulated in fp32 in a
+    fixed order and rounded once.  dx may alias x, ds may alias s; neither may alias g.
+    st: the layer's workspace (HIP path, needed where se_parts(...) > 1)."""
+    B, HW, C = _ch_scale_dims(x, s)
+    if not _native_t(g):
+        g32, s32 = g.float(), s.reshape(B, 1, 1, C).float()
+        dsum = (g32 * x.float()).sum((1, 2))
+        dx.copy_(g32 * s32)
+        ds.copy_(dsum.reshape(ds.shape))
+        return
+    _flat_bf16(g, x, s, dx, ds, who="ch_scale")
+    ws = st.ws if st is not None else None
+    native.check(_k().cxn_ch_scale_bwd(g.data_ptr(), x.data_ptr(), s.data_ptr(), dx.data_ptr(), ds.data_ptr(),
+                                       ws.data_ptr() if ws is not None else None,
+                                       ws.numel() if ws is not None else 0, B, HW, C, _stream()), "ch_scale_bwd")
 
 
 # ----------------------------------------------------------------------------- prelu

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -290,6 +291,13 @@ def pool_forward(x, y, state, KH, KW, S, P, mode: str, relu=False, mark_mask=Fal
         if state is not None and arg is not None:
             state.copy_(arg)
         return
+    if GLOBAL_POOL and pool_global_native(mode, H, W, C, KH, KW, P, Ho, Wo, relu=relu, nonneg=nonneg):
+        parts = int(_k().cxn_se_parts(N, H * W, C))
+        ws = workspace("global_pool", parts * N * C, x.device, 1 << 16) if parts > 1 else None
+        native.check(_k().cxn_global_pool_fwd(x.data_ptr(), y.data_ptr(), ws.data_ptr() if ws is not None else None,
+                                              ws.numel() if ws is not None else 0, N, H * W, C,
+                                              1.0 / (KH * KW) if m == 2 else 1.0, _stream()), "global_pool_fwd")
+        return
     flags = int(bool(relu)) | (2 if (mark_mask and m == 0 and KH * KW < 128 and state is not None) else 0)
     flags |= 4 if nonneg else 0
     native.check(_k().cxn_pool_fwd(x.data_ptr(), y.data_ptr(),
@@ -300,6 +308,25 @@ def pool_forward(x, y, state, KH, KW, S, P, mode: str, relu=False, mark_mask=Fal
 def pool_mask_in_state(mode: str, KH: int, KW: int) -> bool:
     """Whether pool_forward(mark_mask=True) encodes relu' in the max offsets."""
     return POOL_MODE[mode] == 0 and KH * KW < 128
+
+
+# windows of up to this many elements stay on pool_fwd / pool_fwd_rows: every global pooling of
+# the nets before squeeze-and-excitation (7 x 7 = 49, 6 x 6, 3 x 3) keeps the kernel it had
+GLOBAL_POOL_MIN_WINDOW = 64
+# CXXNET_GLOBAL_POOL=0 (or setting this False) sends every pooling to the generic kernels
+# (benchmarks/se_probe.py times one against the other)
+GLOBAL_POOL = os.environ.get("CXXNET_GLOBAL_POOL", "1") != "0"
+
+
+def pool_global_native(mode: str, H: int, W: int, C: int, KH: int, KW: int, P: int, Ho: int, Wo: int,
+                       relu=False, nonneg=False) -> bool:
+    """Whether pool_forward's native path runs the global sum / avg kernel
+    (csrc/kernels/se_kernels.hip: one lane per 8 channels of an image walking the map, fixed-order
+    fp32 partials) instead of pool_fwd_rows' one lane per output: sum or avg mode, the window
+    exactly the whole map (pad 0, one output), C % 8 == 0, no relu flags, and a window of more than
+    GLOBAL_POOL_MIN_WINDOW elements."""
+    return (POOL_MODE[mode] in (1, 2) and KH == H and KW == W and P == 0 and Ho == 1 and Wo == 1 and C % 8 == 0
+            and not relu and not nonneg and KH * KW > GLOBAL_POOL_MIN_WINDOW)
 
 
 def pool_backward(x, state, dy, dx, KH, KW, S, P, mode: str, relu=False, dbias=None):
