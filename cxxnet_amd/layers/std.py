@@ -637,6 +637,13 @@ class PoolingLayer(Layer):
                "kernel size exceed input")
         ho = ops.pool_out_size(h, lp.kernel_height, lp.stride, lp.pad_y)
         wo = ops.pool_out_size(w, lp.kernel_width, lp.stride, lp.pad_x)
+        # with a pad the ceil rule can give a last window that starts at or past the map's edge (5 / k 2 /
+        # s 2 / pad 1: window 3 starts at row 5), and a pad >= the kernel a first one that ends before it:
+        # no element to pool (max would give -inf, NaN downstream)
+        for axis, size, k, pad, n in (("height", h, lp.kernel_height, lp.pad_y, ho), ("width", w, lp.kernel_width, lp.pad_x, wo)):
+            _check(pad < k and (n - 1) * lp.stride - pad < size,
+                   "PoolingLayer: a window lies wholly in the padding (%s %d, kernel %d, stride %d, pad %d gives %d "
+                   "windows)" % (axis, size, k, lp.stride, pad, n))
         nodes_out[0].set_shape(b, c, ho, wo, cp=nodes_in[0].cp)
 
     def _state(self, y: Node):

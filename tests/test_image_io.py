@@ -102,7 +102,9 @@ def test_imgbinx_shuffle_is_permutation(imgset):
 
 def test_mean_value_mirror_scale(imgset):
     d, arrays = imgset
-    it = create_iterator(_cfg("img", d, mean_value="10,20,30", mirror=1, scale=0.5))
+    # decode_gpu = 0: the host pixel batch this test describes (with a GPU present the default hands
+    # the decode's second half to the device and the batch is a JpegCoefImages)
+    it = create_iterator(_cfg("img", d, mean_value="10,20,30", mirror=1, scale=0.5, decode_gpu=0))
     it.init()
     assert it.next()
     b = it.value()
@@ -325,7 +327,8 @@ def test_native_decode_iterator_matches_its_crop_params(jpegset, kind):
     runs = []
     for nt in (1, 4):
         it = create_iterator(_cfg(kind, d, rand_crop=1, rand_mirror=1, seed_data=2, mean_value="1,2,3",
-                                  decode_native=1, decode_native_threads=nt, round_batch=1))
+                                  decode_native=1, decode_native_threads=nt, round_batch=1,
+                                  decode_gpu=0))  # the host pixel path (the default with a GPU is the device's)
         it.init()
         assert it._jpeg is not None and it._jpeg.threads == nt
         batches = []

@@ -192,6 +192,35 @@ input_shape = 2,9,9
     assert torch.allclose(ours[(3, "bias")], bf.grad, rtol=1e-4, atol=1e-6)
 
 
+POOL_PAD_NET = """
+netconfig=start
+layer[0->1] = max_pooling
+  kernel_size = 2
+  stride = 2
+  pad = 1
+layer[1->2] = flatten
+layer[2->3] = fullc:f
+  nhidden = 4
+layer[3->3] = softmax
+netconfig=end
+input_shape = 2,%d,%d
+"""
+
+
+def test_pooling_refuses_a_window_wholly_in_the_padding():
+    """5 / kernel 2 / stride 2 / pad 1: the ceil rule gives 4 windows and the last starts at row 5,
+    past the map (max would pool nothing: -inf).  Refused at setup on either axis, with the sizes
+    in the message; the neighbouring 6 (4 windows, the last holds row 5) is accepted."""
+    for h, w, axis in ((5, 6, "height 5"), (6, 5, "width 5")):
+        with pytest.raises(ValueError, match="wholly in the padding.*%s, kernel 2, stride 2, pad 1 gives 4" % axis):
+            make(POOL_PAD_NET % (h, w), 2)
+    tr = make(POOL_PAD_NET % (6, 6), 2)
+    assert tuple(tr.net.nodes[1].shape[2:]) == (4, 4)
+    tr.net.set_input(torch.randn(2, 2, 6, 6))
+    tr.net.forward(False)
+    assert torch.isfinite(tr.net.nodes[1].data.float()).all()
+
+
 def test_batch_norm_and_prelu_gradients():
     conf = """
 netconfig=start
