@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -97,31 +98,66 @@ def build_kernels(verbose=False, force=False, jobs=8) -> str:
     if force or _newer(target, objs) or jobs_list:
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", target + ".tmp"], verbose)
         _check_stubs(target + ".tmp")
+        _check_exports(target + ".tmp")
         os.replace(target + ".tmp", target)
     return target
+
+
+def _dyn_symbols(lib, which):
+    """(tool name, output lines) for the dynamic symbols of lib that are `which` ("defined" or
+    "undefined"), or None when there is no tool: ROCm's llvm-nm, else nm from PATH, else llvm-readelf."""
+    llvm = os.path.join(ROCM, "lib", "llvm", "bin")
+    for tool, args in ((os.path.join(llvm, "llvm-nm"), ["-D", f"--{which}-only"]),
+                       (shutil.which("nm"), ["-D", f"--{which}-only"]),
+                       (os.path.join(llvm, "llvm-readelf"), ["--dyn-syms", "-W"])):
+        if tool and os.path.exists(tool):
+            break
+    else:
+        return None
+    lines = _run([tool, *args, lib], False).splitlines()
+    if "readelf" in tool:  # lists every dynamic symbol: the undefined ones have section index UND
+        lines = [l for l in lines if (" UND " in l) == (which == "undefined")]
+    return os.path.basename(tool), lines
 
 
 def _check_stubs(lib):
     """Fail the build when a kernel's host launch stub is undefined: hipcc's host pass can drop
     one silently (a builtin called directly inside a kernel's lambdas, see lds_dma16 in
     gfx950_prims.h; a launch moved into a generic lambda is the same hazard), and the library would
-    then fail only at dlopen on a GPU box.  Uses ROCm's llvm-nm, else nm from PATH, else
-    llvm-readelf; skipped only when none of them exists."""
-    llvm = os.path.join(ROCM, "lib", "llvm", "bin")
-    for tool, args in ((os.path.join(llvm, "llvm-nm"), ["-D", "--undefined-only"]),
-                       (shutil.which("nm"), ["-D", "--undefined-only"]),
-                       (os.path.join(llvm, "llvm-readelf"), ["--dyn-syms", "-W"])):
-        if tool and os.path.exists(tool):
-            break
-    else:
+    then fail only at dlopen on a GPU box.  Skipped only when no symbol tool exists (_dyn_symbols)."""
+    found = _dyn_symbols(lib, "undefined")
+    if found is None:
         return
-    out = _run([tool, *args, lib], False)
-    # (readelf lists every dynamic symbol: the undefined ones have section index UND)
-    bad = [l.split()[-1] for l in out.splitlines()
-           if "__device_stub__" in l and ("readelf" not in tool or " UND " in l)]
+    tool, lines = found
+    bad = [l.split()[-1] for l in lines if "__device_stub__" in l]
     if bad:
         raise RuntimeError(f"build failed: {len(bad)} undefined kernel launch stub(s) in {lib}, e.g. {bad[0]}")
-    print(f"stub check ({os.path.basename(tool)}): 0 undefined __device_stub__ symbols in {KERNEL_LIB}")
+    print(f"stub check ({tool}): 0 undefined __device_stub__ symbols in {KERNEL_LIB}")
+
+
+def _export_mismatch(symbol_lines, declared):
+    """(declared but not exported, exported but not declared): the names cxn_api.h declares against
+    the cxn_* functions among a library's defined dynamic symbols (nm or readelf lines; data symbols
+    such as cxn_deterministic are no entry points)."""
+    exported = {l.split()[-1] for l in symbol_lines
+                if re.search(r" ([TW]|FUNC) .*\bcxn_\w+$", l)}
+    return sorted(set(declared) - exported), sorted(exported - set(declared))
+
+
+def _check_exports(lib):
+    """Fail the build when the library's exported cxn_* functions and the prototypes of cxn_api.h
+    differ.  The compiler checks every declared definition against its prototype; an entry point
+    defined without one would load with ctypes' default signature, and a prototype without a
+    definition would fail only at load.  Skipped where _check_stubs is."""
+    from . import native
+    found = _dyn_symbols(lib, "defined")
+    if found is None:
+        return
+    undefined, undeclared = _export_mismatch(found[1], native._API)
+    if undefined or undeclared:
+        raise RuntimeError(f"build failed: {lib} and cxn_api.h disagree: declared but not exported "
+                           f"{undefined}, exported but not declared {undeclared}")
+    print(f"export check ({found[0]}): {len(native._API)} cxn_* entry points match cxn_api.h")
 
 
 def build_wrapper(verbose=False, force=False) -> str:

@@ -26,8 +26,6 @@ struct Dst4 {
   bf16_t *p[4];
 };
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // cnt elements (8 on the vector path) of a run starting at p
 template <bool VEC>
 __device__ __forceinline__ void load_run(const bf16_t *p, int cnt, float *f) {

@@ -55,8 +55,6 @@ static long max_partials(long rows, int C, bool vec) {
   return byrows < pmax ? byrows : pmax;
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int V> __device__ __forceinline__ void load_v(const bf16_t *p, float *f);
 template <> __device__ __forceinline__ void load_v<8>(const bf16_t *p, float *f) {
   unpack8(*reinterpret_cast<const uint4 *>(p), f);

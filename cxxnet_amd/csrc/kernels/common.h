@@ -6,7 +6,7 @@
 #include <functional>
 #include <vector>
 
-#define CXN_API extern "C" __attribute__((visibility("default")))
+#include "cxn_api.h"  // CXN_API, CxnOperand and the prototype of every exported entry point
 
 typedef unsigned short bf16_t;  // storage type for bf16 tensors
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -128,6 +128,9 @@ static inline int nblocks(long n, int per_block = 256, int cap = 256 * 16) {
 // -3 when a launch failed.
 #define S_ static_cast<hipStream_t>(stream)
 #define RET return hipGetLastError() == hipSuccess ? 0 : -3
+
+// 16-byte alignment, what the vectorised (uint4) paths need of every pointer they touch
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Deterministic mode (cxn_set_deterministic): reductions that would combine partial sums with
 // atomics in a run-dependent order (cross-block channel sums, bias-grad partials) use one

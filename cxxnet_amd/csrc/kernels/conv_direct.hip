@@ -1056,7 +1056,7 @@ CXN_API long cxn_conv_direct(const void *x, int ldx, const void *w, const float 
   a.groups = groups;
   a.relu = relu;
   a.dbp_ld = groups * Cog;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   if (variant < 0 || variant > 3) return -1;
   int rc;
   if (m14) {
@@ -1078,5 +1078,5 @@ CXN_API long cxn_conv_direct(const void *x, int ldx, const void *w, const float 
     rc = launch_cd<13, 13, 3, IPB, 4, 4>(a, epi, variant, db, s);
   }
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }

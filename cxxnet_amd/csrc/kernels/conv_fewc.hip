@@ -193,5 +193,5 @@ CXN_API int cxn_conv_fewc_fwd(const void *x, const void *w, const float *bias, v
     default: return -1;
   }
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }

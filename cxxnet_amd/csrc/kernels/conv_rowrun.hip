@@ -246,7 +246,7 @@ CXN_API int cxn_conv_rowrun_fwd(const void *x, long x_bytes, const void *w, cons
   const bf16_t *xb = static_cast<const bf16_t *>(x);
   const bf16_t *wb = static_cast<const bf16_t *>(w);
   bf16_t *yb = static_cast<bf16_t *>(y);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   int rc = -1;
   switch (Cout / 32) {
     case 1: rc = launch<1>(xb, x_bytes, wb, bias, yb, N, H, W, C, Ho, Wo, KH, LP, S, ldc, relu, s); break;
@@ -256,6 +256,6 @@ CXN_API int cxn_conv_rowrun_fwd(const void *x, long x_bytes, const void *w, cons
     default: return -1;
   }
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 

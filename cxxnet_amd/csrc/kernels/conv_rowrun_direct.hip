@@ -583,11 +583,11 @@ CXN_API long cxn_conv_wgrad_rowrun(const void *x, const void *dy, float *dw, flo
   if (!ok) return ws ? -1 : 0;
   if (!ws) return geo == 0 ? RrLaunch<GAlex>::ws(N, Ho) : RrLaunch<GGoog>::ws(N, Ho);
   const bf16_t *xb = static_cast<const bf16_t *>(x), *dyb = static_cast<const bf16_t *>(dy);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   const int rc = geo == 0 ? RrLaunch<GAlex>::run(xb, dyb, dw, ws, ws_floats, N, H, Ho, ldy, alpha, s)
                           : RrLaunch<GGoog>::run(xb, dyb, dw, ws, ws_floats, N, H, Ho, ldy, alpha, s);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 
 // Few-channel first layer forward (conv_rowrun_fwd2).  Served: the geometries of
@@ -602,8 +602,8 @@ CXN_API int cxn_conv_rowrun_fwd2(const void *x, const void *w, const float *bias
   if (!ok) return -1;
   const bf16_t *xb = static_cast<const bf16_t *>(x), *wb = static_cast<const bf16_t *>(w);
   bf16_t *yb = static_cast<bf16_t *>(y);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   if (geo == 0) launch_fwd2<GAlex>(xb, wb, bias, yb, N, H, Ho, ldc, relu, s);
   else launch_fwd2<GGoog>(xb, wb, bias, yb, N, H, Ho, ldc, relu, s);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }

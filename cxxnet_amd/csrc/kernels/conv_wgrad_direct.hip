@@ -721,26 +721,26 @@ CXN_API long cxn_conv_wgrad_direct(const void *x, const void *dy, float *dw, flo
   if (Cg % 16 || Cog % 64 || C % 8 || ldy % 8 || groups < 1 || C < groups * Cg || ldy < groups * Cog) return ws ? -1 : 0;
   if (KH == 3 && Cg % 32) return ws ? -1 : 0;
   if (static_cast<long>(N) * H * W * (C > ldy ? C : ldy) >= (1L << 30)) return ws ? -1 : 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   const bf16_t *xb = static_cast<const bf16_t *>(x), *dyb = static_cast<const bf16_t *>(dy);
   if (KH == 5 && H == 27 && W == 27 && db == nullptr && Cg % 16 == 0 && Cog % 64 == 0) {  // tap-split form (conv2)
     // eight waves (2 per SIMD, K-steps alternating) over four: 119 vs 141 us at AlexNet b256
     if (!ws) return ws_wt<27, 27, 5, 14, 4, 8>(N, Cg, Cog, groups, splits);
     const int rc = launch_wt<27, 27, 5, 14, 4, 8>(xb, dyb, dw, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
     if (rc != 0) return rc;
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    RET;
   }
   if (KH == 3 && H == 13 && W == 13) {
     if (!ws) return ws_wd<13, 13, 3, 2>(N, Cg, Cog, groups, splits);
     const int rc = launch_wd<13, 13, 3, 2>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
     if (rc != 0) return rc;
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    RET;
   }
   if (KH == 3 && H == 14 && W == 14) {  // (VGG-16 conv5_x, GoogLeNet 4c / 4e): one image per stage
     if (!ws) return ws_wd<14, 14, 3, 1>(N, Cg, Cog, groups, splits);
     const int rc = launch_wd<14, 14, 3, 1>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
     if (rc != 0) return rc;
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    RET;
   }
   return ws ? -1 : 0;
 }

@@ -49,8 +49,6 @@ struct Dims {
   FastDiv dWr, dHWr;
 };
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static bool make_dims(Dims &d, int N, int H, int W, int Hs, int Ws, int C, int py, int px, long ps_item, long ps_src,
                       int run) {
   d.N = N; d.H = H; d.W = W; d.Hs = Hs; d.Ws = Ws; d.py = py; d.px = px;

@@ -549,15 +549,6 @@ CXN_API int cxn_gemm_set_group(int group_i) {
   return old;
 }
 
-// Same operand record as cxn_gemm (gemm_mfma.hip).
-struct CxnOperandG {
-  const void *ptr;
-  long gstride;
-  long nbytes;
-  int ld, rows, kdim;
-  int H, W, C, Ho, Wo, KH, KW, stride, pad_h, pad_w, dil, Cg;
-};
-
 namespace {
 // Byte alignment the kernel-row runs of the row gathers need (their 16-byte DMAs start at a
 // pixel's first element): every image row (W*C*2 bytes) and every output-pixel step
@@ -568,10 +559,10 @@ static const int g_rowrun_align = [] {
   const int v = e ? atoi(e) : 8;
   return v > 0 ? v : 8;
 }();
-bool rowrun_aligned(const CxnOperandG *o) {
+bool rowrun_aligned(const CxnOperand *o) {
   return (o->W * o->C * 2) % g_rowrun_align == 0 && (o->stride * o->C * 2) % g_rowrun_align == 0;
 }
-bool supported(const CxnOperandG *o, int mode) {
+bool supported(const CxnOperand *o, int mode) {
   if (o->nbytes >= (1L << 31) || (reinterpret_cast<uintptr_t>(o->ptr) & 15) || o->gstride % 8 != 0) return false;
   if (mode == K_DIRECT || mode == MN_DIRECT) return o->ld % 8 == 0 && (mode == K_DIRECT || o->rows % 8 == 0);
   if (mode == K_ROWGATHER)  // whole kernel rows read as runs: no padding, one group, aligned pixels
@@ -584,7 +575,7 @@ bool supported(const CxnOperandG *o, int mode) {
   if (o->C % 8 != 0 && !row_runs) return false;
   return mode == K_GATHER || o->rows % 8 == 0;
 }
-void fill(GOperand &r, const CxnOperandG *o, int mode) {
+void fill(GOperand &r, const CxnOperand *o, int mode) {
   r.ptr = static_cast<const bf16_t *>(o->ptr);
   r.gstride = o->gstride;
   r.nbytes = static_cast<uint32_t>(o->nbytes);
@@ -611,7 +602,7 @@ void fill(GOperand &r, const CxnOperandG *o, int mode) {
 // Returns 0 on success, -1 unsupported configuration (the caller falls back), -3 launch error.
 // Requirements: kdim % 8 == 0; 16-byte aligned rows; MN-major operands: rows % 8 == 0;
 // gathers: Cg % 8 == 0 and dil == 1; every buffer < 2 GiB.
-CXN_API int cxn_gemm_glds(const CxnOperandG *a, const CxnOperandG *b, int amode, int bmode, void *out,
+CXN_API int cxn_gemm_glds(const CxnOperand *a, const CxnOperand *b, int amode, int bmode, void *out,
                           long out_gstride, int ldc, float alpha, const float *bias, long bias_gstride, int relu,
                           int mask_relu, int epi, int tile, int groups, int ksplit, long kstride, float *dbias,
                           float *dws, long dws_elems, int dws_ld, void *stream) {
@@ -626,17 +617,16 @@ CXN_API int cxn_gemm_glds(const CxnOperandG *a, const CxnOperandG *b, int amode,
   if (epi == EPI_F32_SGD) return -1;  // only through cxn_gemm_glds_sgd
   GEpi E{out, out_gstride, ldc, alpha, bias, bias_gstride, relu, mask_relu, kstride,
          nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, dws, dws_ld, dws_elems, dbias, g_gemm_group_i};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = dispatch(amode, bmode, epi, tile, A, B, E, groups < 1 ? 1 : groups, ksplit < 1 ? 1 : ksplit, s);
+  const int rc = dispatch(amode, bmode, epi, tile, A, B, E, groups < 1 ? 1 : groups, ksplit < 1 ? 1 : ksplit, S_);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 
 // cxn_gemm_glds with a second bf16 source added in the epilogue: out = mask(acc + add), add laid out
 // like out (row stride ldc, group stride out_gstride).  The gemm_glds tiles of the dispatch switch
 // only (not 114 / 130-142, whose epilogues do not read it); conv data-gradient operands (K_DIRECT
 // weights x K_GATHER dy), no bias, no split-K.
-CXN_API int cxn_gemm_glds_add(const CxnOperandG *a, const CxnOperandG *b, int amode, int bmode, void *out,
+CXN_API int cxn_gemm_glds_add(const CxnOperand *a, const CxnOperand *b, int amode, int bmode, void *out,
                               long out_gstride, int ldc, const void *add, int mask_relu, int tile, int groups,
                               void *stream) {
   if (a->kdim != b->kdim || add == nullptr || (ldc & 7) || tile == 114 || (tile >= 130 && tile <= 142)) return -1;
@@ -650,17 +640,16 @@ CXN_API int cxn_gemm_glds_add(const CxnOperandG *a, const CxnOperandG *b, int am
          nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, nullptr, 0, 0, nullptr, g_gemm_group_i};
   E.add = static_cast<const bf16_t *>(add);
   if (amode != K_DIRECT || bmode != K_GATHER) return -1;  // the one instantiated form
-  const int rc = dispatch(amode, bmode, EPI_BF16_ADD, tile, A, B, E, groups < 1 ? 1 : groups, 1,
-                          static_cast<hipStream_t>(stream));
+  const int rc = dispatch(amode, bmode, EPI_BF16_ADD, tile, A, B, E, groups < 1 ? 1 : groups, 1, S_);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 
 // cxn_gemm_glds with two bf16 destinations: output columns [0, split_i) to out (row stride
 // ldc), [split_i, rows of A) to out2 (row stride ldc2) -- the sibling 1x1 convs of an inception
 // module as one GEMM (NeuralNet._fuse_siblings).  Only the gemm_glds tiles of the dispatch switch
 // (not 114 / 130-142, whose epilogues have one destination); EPI_BF16, no split-K.
-CXN_API int cxn_gemm_glds_split(const CxnOperandG *a, const CxnOperandG *b, int amode, int bmode, void *out, int ldc,
+CXN_API int cxn_gemm_glds_split(const CxnOperand *a, const CxnOperand *b, int amode, int bmode, void *out, int ldc,
                                 void *out2, int ldc2, int split_i, const float *bias, int relu, int tile,
                                 void *stream) {
   if (a->kdim != b->kdim || split_i <= 0 || split_i % 8 != 0 || split_i >= a->rows || (ldc & 7) || (ldc2 & 7))
@@ -677,10 +666,9 @@ CXN_API int cxn_gemm_glds_split(const CxnOperandG *a, const CxnOperandG *b, int 
   E.out2 = out2;
   E.ldc2 = ldc2;
   E.split_i = split_i;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = dispatch(amode, bmode, EPI_BF16, tile, A, B, E, 1, 1, s);
+  const int rc = dispatch(amode, bmode, EPI_BF16, tile, A, B, E, 1, 1, S_);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 
 // The streaming form of the fused fc weight-grad + SGD step (fc_wgrad_sgd.hip): 0 = off (every call
@@ -716,7 +704,7 @@ CXN_API long cxn_gemm_sgd_stream_calls() { return g_sgd_stream_calls.load(std::m
 // dw = alpha * B^T A (MN-major x and dy, ldc = nin) the epilogue applies
 //   g = clip(dw); m = mom*m - lr*(g + wd*w); w += m; wb = bf16(w)
 // to the layer's master / momentum / shadow slices instead of storing dw.
-CXN_API int cxn_gemm_glds_sgd(const CxnOperandG *a, const CxnOperandG *b, int ldc, float alpha, float *w, float *m,
+CXN_API int cxn_gemm_glds_sgd(const CxnOperand *a, const CxnOperand *b, int ldc, float alpha, float *w, float *m,
                               void *wb, float lr, float wd, float mom, float clip, const float *hyp, int tile,
                               void *stream) {
   if (a->kdim != b->kdim) return -1;
@@ -730,12 +718,12 @@ CXN_API int cxn_gemm_glds_sgd(const CxnOperandG *a, const CxnOperandG *b, int ld
   fill(B, b, MN_DIRECT);
   GEpi E{nullptr, 0, ldc, alpha, nullptr, 0, 0, 0, 0, w, m, static_cast<bf16_t *>(wb), lr, wd, mom, clip, nullptr, 0, 0, nullptr,
          g_gemm_group_i, hyp};
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = S_;
   if (g_sgd_stream > 0 && cxg::dispatch_fc_sgd_stream(A, B, E, g_sgd_stream >= 2, g_sgd_stream_blocks, s) == 0) {
     g_sgd_stream_calls.fetch_add(1, std::memory_order_relaxed);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    RET;
   }
   const int rc = dispatch(MN_DIRECT, MN_DIRECT, EPI_F32_SGD, tile, A, B, E, 1, 1, s);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }

@@ -615,14 +615,6 @@ int dispatch(const GemmArgs &g, const Operand &A, const Operand &B, const Epilog
 }  // namespace
 
 // Flat C ABI consumed by cxxnet_amd.ops (ctypes).  Returns 0 on success.
-struct CxnOperand {
-  const void *ptr;
-  long gstride;
-  long nbytes;
-  int ld, rows, kdim;
-  int H, W, C, Ho, Wo, KH, KW, stride, pad_h, pad_w, dil, Cg;
-};
-
 static Operand to_operand(const CxnOperand &o, int mode, int vec) {
   Operand r{};
   r.ptr = static_cast<const bf16_t *>(o.ptr);
@@ -655,8 +647,7 @@ CXN_API int cxn_gemm(const CxnOperand *a, const CxnOperand *b, int amode, int bm
   if (A.kdim != B.kdim) return -2;
   if (A.rows <= 0 || B.rows <= 0 || A.kdim <= 0) return 0;
   Epilogue E{out, out_gstride, ldc, alpha, bias, bias_gstride, relu, mask_relu, kstride};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = dispatch(g, A, B, E, s);
+  int rc = dispatch(g, A, B, E, S_);
   if (rc != 0) return rc;
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }

@@ -43,18 +43,16 @@ CXN_API int cxn_rec_size(void *list) { return list ? static_cast<int>(static_cas
 // Re-issue every recorded launch on `stream`; 0, or -3 on a launch error.
 CXN_API int cxn_rec_replay(void *list, void *stream) {
   if (!list) return 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (auto &op : static_cast<cxr::LaunchList *>(list)->ops) op(s);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  for (auto &op : static_cast<cxr::LaunchList *>(list)->ops) op(S_);
+  RET;
 }
 
 // Replay several lists back to back (one call for a run of segments).
 CXN_API int cxn_rec_replay_many(void *const *lists, int n, void *stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
   for (int i = 0; i < n; ++i)
     if (lists[i])
-      for (auto &op : static_cast<cxr::LaunchList *>(lists[i])->ops) op(s);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+      for (auto &op : static_cast<cxr::LaunchList *>(lists[i])->ops) op(S_);
+  RET;
 }
 
 CXN_API void cxn_rec_free(void *list) { delete static_cast<cxr::LaunchList *>(list); }
@@ -62,7 +60,7 @@ CXN_API void cxn_rec_free(void *list) { delete static_cast<cxr::LaunchList *>(li
 // Device-to-device copy of `bytes` bytes on `stream` (recorded when a list is open).
 CXN_API int cxn_copy_d2d(void *dst, const void *src, long bytes, void *stream) {
   if (bytes <= 0) return 0;
-  return CXN_MEMCPY_D2D(dst, src, static_cast<size_t>(bytes), static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -3;
+  return CXN_MEMCPY_D2D(dst, src, static_cast<size_t>(bytes), S_) == hipSuccess ? 0 : -3;
 }
 
 namespace {
@@ -129,14 +127,13 @@ CXN_API int cxn_zero_ranges(float *base, const long *off, const long *len, int n
   }
   r.n = n;
   const long blocks = (mx / 4 + 255) / 256 + 1;
-  CXN_LAUNCH(zero_ranges_k, dim3(static_cast<unsigned>(blocks < 1024 ? blocks : 1024), n), dim3(256), 0,
-             static_cast<hipStream_t>(stream), base, r);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  CXN_LAUNCH(zero_ranges_k, dim3(static_cast<unsigned>(blocks < 1024 ? blocks : 1024), n), dim3(256), 0, S_, base, r);
+  RET;
 }
 
 // Zero `bytes` bytes at dst on `stream` (recorded when a list is open): gradient zeroing at the
 // start of a backward pass must be part of the replayed step.
 CXN_API int cxn_zero(void *dst, long bytes, void *stream) {
   if (bytes <= 0) return 0;
-  return CXN_MEMSET(dst, 0, static_cast<size_t>(bytes), static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -3;
+  return CXN_MEMSET(dst, 0, static_cast<size_t>(bytes), S_) == hipSuccess ? 0 : -3;
 }

@@ -115,7 +115,6 @@ __global__ void scale_f32(float *__restrict__ x, long n, float s) {
 // segs: packed [nseg][6] doubles-as-floats: off, n, lr, wd, mom, clip
 CXN_API int cxn_fused_update(const long *offs, const long *ns, const float *hyper /*[nseg][4]*/, int nseg, float *w,
                              float *g, float *st1, float *st2, void *wb, int algo, float d1, float d2, void *stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
   for (int base = 0; base < nseg; base += MAX_SEG) {
     SegTable tab;
     const int cnt = nseg - base < MAX_SEG ? nseg - base : MAX_SEG;
@@ -128,25 +127,25 @@ CXN_API int cxn_fused_update(const long *offs, const long *ns, const float *hype
     long bx = (maxn + NT * 4 - 1) / (NT * 4);
     if (bx > 2048) bx = 2048;
     dim3 grid(static_cast<unsigned>(bx), cnt);
-    CXN_LAUNCH((fused_update), grid, NT, 0, s, tab, w, g, st1, st2, static_cast<bf16_t *>(wb), algo, d1, d2);
+    CXN_LAUNCH((fused_update), grid, NT, 0, S_, tab, w, g, st1, st2, static_cast<bf16_t *>(wb), algo, d1, d2);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
 
 CXN_API int cxn_nonfinite_check(const float *g, long n, int *flag, void *stream) {
   long b = (n + NT * 8 - 1) / (NT * 8);
   if (b > 1024) b = 1024;
   if (b < 1) b = 1;
-  CXN_LAUNCH((nonfinite_check), b, NT, 0, static_cast<hipStream_t>(stream), g, n, flag);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  CXN_LAUNCH((nonfinite_check), b, NT, 0, S_, g, n, flag);
+  RET;
 }
 
 CXN_API int cxn_scale_f32(float *x, long n, float sc, void *stream) {
   long b = (n + NT * 8 - 1) / (NT * 8);
   if (b > 2048) b = 2048;
   if (b < 1) b = 1;
-  CXN_LAUNCH((scale_f32), b, NT, 0, static_cast<hipStream_t>(stream), x, n, sc);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  CXN_LAUNCH((scale_f32), b, NT, 0, S_, x, n, sc);
+  RET;
 }
 
 // *p += v on the device (the step counter that dropout seeds and the updaters read): a library
@@ -155,6 +154,6 @@ __global__ void add_i32(int *p, int v) {
   if (threadIdx.x == 0) *p += v;
 }
 CXN_API int cxn_add_i32(int *p, int v, void *stream) {
-  CXN_LAUNCH((add_i32), 1, 64, 0, static_cast<hipStream_t>(stream), p, v);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  CXN_LAUNCH((add_i32), 1, 64, 0, S_, p, v);
+  RET;
 }

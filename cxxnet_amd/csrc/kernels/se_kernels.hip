@@ -40,8 +40,6 @@ constexpr int TARGET_BLOCKS = 2048;  // 8 per CU
 constexpr int FWD_MIN_PIX = 2;
 constexpr int RED_MIN_PIX = 8;
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 struct Geo {
   int V, G, GX, RL, ny;
 };

@@ -116,5 +116,5 @@ CXN_API int cxn_image_warp(const void *src, const void *table, const void *wtab,
   if (r1 == r0) return 0;
   CXN_LAUNCH((image_warp), dim3(cdiv(w, 16), cdiv(h, 16), r1 - r0), 256, 0, S_, (const uint8_t *)src,
              (const long long *)table + static_cast<long>(r0) * kTable, (const int *)wtab, h, w, C, (uint8_t *)out);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  RET;
 }
