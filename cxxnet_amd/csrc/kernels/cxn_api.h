@@ -205,6 +205,11 @@ CXN_API int cxn_add_fwd(const void *x0, const void *x1, const void *x2, const vo
 CXN_API int cxn_add_bwd(const void *g, const void *mask, void *d0, void *d1, void *d2, void *d3, int n_out, long n,
                         void *stream);
 
+// hact_kernels.hip
+CXN_API long cxn_hact_pass_elems();
+CXN_API int cxn_hact_fwd(const void *x, void *y, long n, int kind, void *stream);
+CXN_API int cxn_hact_bwd(const void *x, const void *g, void *dx, long n, int kind, void *stream);
+
 // se_kernels.hip
 CXN_API int cxn_se_parts(long B, long HW, int C);
 CXN_API long cxn_se_ws_floats(long Bmax, long HW, int C);

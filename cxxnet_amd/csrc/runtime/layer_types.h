@@ -43,6 +43,9 @@ enum : int {
   kBatchNormMA = 40,
   kAdd = 41,
   kChScale = 42,
+  kRelu6 = 43,
+  kHSigmoid = 44,
+  kHSwish = 45,
   kPairTestGap = 1024,
 };
 
@@ -62,6 +65,7 @@ inline int GetLayerType(const std::string &t) {
       {"l2_loss", kL2Loss}, {"multi_logistic", kMultiLogistic},
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
       {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
+      {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,11 +1,11 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
-insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add and
-ch_scale.
+insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
+ch_scale and relu6 / hsigmoid / hswish.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
 csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, ch_scale in
-csrc/kernels/se_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
+csrc/kernels/se_kernels.hip, relu6 / hsigmoid / hswish in csrc/kernels/hact_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
 from __future__ import annotations
@@ -457,6 +457,45 @@ class ChScaleLayer(Layer):
         L.ch_scale_backward(nodes_out[0].data, x.data, s.data, x.gdst, s.gdst, self._st)
 
 
+class HardActLayer(Layer):
+    """`relu6` (type id 43), `hsigmoid` (44), `hswish` (45) -- extensions, no reference
+    counterpart: the bounded activations of the mobile nets, 1 -> 1 on nodes of any shape.  fp32
+    arithmetic, one rounding to the node's dtype; a breakpoint belongs to the outer piece:
+        relu6     y = +0 (x <= 0), x (0 < x < 6), 6 (x >= 6)
+        hsigmoid  y = +0 (x <= -3), (x + 3) / 6 (-3 < x < 3), 1 (x >= 3)
+        hswish    y = 0 (x <= -3), x (x + 3) / 6 (-3 < x < 3), x (x >= 3)
+    Backward takes the derivative from the INPUT node (hswish is not monotonic, so its output
+    cannot stand in for x): with g the gradient held by the output node, dx = g f'(x) goes to
+    x.gdst, which may be x.data.  So the layer never writes its input in forward and reads it
+    again in backward: the output node must differ from the input node, for all three types.
+    The output is not claimed non-negative.  No parameters and no state: the checkpoint holds
+    nothing for it."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+
+    def __init__(self, ctx, kind):
+        super().__init__(ctx)
+        _check(kind in L.HACT_KINDS, "HardActLayer: unknown kind " + repr(kind))
+        self.kind = kind
+        self.type_name = kind
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "HardActLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "HardActLayer: %s reads its input again in backward, so the output node must differ from the input "
+               "(no self-loop)" % self.kind)
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "HardActLayer: padded-channel input is not supported")
+        nodes_out[0].set_shape(*nodes_in[0].shape)
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        L.hact_forward(self.kind, nodes_in[0].data, nodes_out[0].data)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if prop_grad:
+            L.hact_backward(self.kind, nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -769,6 +808,9 @@ def _register():
     register(40, BatchNormMALayer)
     register(41, AddLayer)
     register(42, ChScaleLayer)
+    register(43, lambda ctx: HardActLayer(ctx, "relu6"))
+    register(44, lambda ctx: HardActLayer(ctx, "hsigmoid"))
+    register(45, lambda ctx: HardActLayer(ctx, "hswish"))
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -1,5 +1,6 @@
 """Model zoo: .conf network definitions (AlexNet, GoogLeNet/Inception-v1, VGG-16, ResNet-18,
-SE-ResNet-18, MobileNet-v1, MNIST MLP/conv, Kaggle-bowl convnet) and helpers to load them."""
+SE-ResNet-18, MobileNet-v1, MobileNet-v3-Large, MNIST MLP/conv, Kaggle-bowl convnet) and helpers
+to load them."""
 from __future__ import annotations
 
 import os

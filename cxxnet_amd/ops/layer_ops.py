@@ -322,6 +322,74 @@ def ch_scale_backward(g, x, s, dx, ds, st: ChScaleState = None):
                                        ws.numel() if ws is not None else 0, B, HW, C, _stream()), "ch_scale_bwd")
 
 
+# ----------------------------------------------------------------------------- relu6 / hsigmoid / hswish
+HACT_KINDS = ("relu6", "hsigmoid", "hswish")  # index = the kernels' kind (csrc/kernels/hact_kernels.hip)
+
+
+def hact_pass_elems() -> int:
+    """Elements one pass of the kernels' capped grid covers; a larger tensor makes a thread take a
+    second grid-stride trip."""
+    return int(_k().cxn_hact_pass_elems())
+
+
+def _hact_kind(kind) -> int:
+    if kind not in HACT_KINDS:
+        raise ValueError("hact: kind must be one of %s, not %r" % (", ".join(HACT_KINDS), kind))
+    return HACT_KINDS.index(kind)
+
+
+def hact_forward(kind: str, x, y):
+    """y = f(x) in fp32, one rounding to y's dtype; the breakpoints belong to the outer pieces:
+    relu6     +0 for x <= 0, 6 for x >= 6, x (the same bits) between;
+    hsigmoid  +0 for x <= -3, 1 for x >= 3, (x + 3) / 6 between;
+    hswish    0 for x <= -3, x (the same bits) for x >= 3, x (x + 3) / 6 between.
+    y must not alias x."""
+    k = _hact_kind(kind)
+    if x.numel() != y.numel():
+        raise ValueError("hact: x and y of one size expected")
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("hact: y must not alias x (backward reads x again)")
+    if not _native_t(x):
+        v = x.float()
+        zero = torch.zeros_like(v)
+        if k == 0:
+            out = torch.where(v <= 0, zero, torch.where(v >= 6, torch.full_like(v, 6.0), v))
+        elif k == 1:
+            out = torch.where(v <= -3, zero, torch.where(v >= 3, torch.ones_like(v), (v + 3.0) / 6.0))
+        else:
+            out = torch.where(v <= -3, zero, torch.where(v >= 3, v, v * (v + 3.0) / 6.0))
+        y.copy_(out.view(y.shape))
+        return
+    _flat_bf16(x, y, who="hact")
+    native.check(_k().cxn_hact_fwd(x.data_ptr(), y.data_ptr(), x.numel(), k, _stream()), "hact_fwd")
+
+
+def hact_backward(kind: str, x, g, dx):
+    """dx = g f'(x), the derivative taken from the layer's INPUT x, in fp32, one rounding:
+    relu6     g (the same bits) for 0 < x < 6, 0 elsewhere;
+    hsigmoid  g / 6 for -3 < x < 3, 0 elsewhere;
+    hswish    0 for x <= -3, g (the same bits) for x >= 3, g (2 x + 3) / 6 between.
+    dx may alias x; it must not alias g."""
+    k = _hact_kind(kind)
+    if not x.numel() == g.numel() == dx.numel():
+        raise ValueError("hact: x, g and dx of one size expected")
+    if dx.data_ptr() == g.data_ptr():
+        raise ValueError("hact: dx must not alias g (it may alias x)")
+    if not _native_t(g):
+        v, gv = x.float(), g.float().view(x.shape)
+        zero = torch.zeros_like(gv)
+        if k == 0:
+            out = torch.where((v > 0) & (v < 6), gv, zero)
+        elif k == 1:
+            out = torch.where((v > -3) & (v < 3), gv / 6.0, zero)
+        else:
+            out = torch.where(v <= -3, zero, torch.where(v >= 3, gv, gv * (2.0 * v + 3.0) / 6.0))
+        dx.copy_(out.view(dx.shape))
+        return
+    _flat_bf16(x, g, dx, who="hact")
+    native.check(_k().cxn_hact_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), k, _stream()), "hact_bwd")
+
+
 # ----------------------------------------------------------------------------- prelu
 def _prelu_mask_ref(x2d, slope, seed, counter, rnd):
     rows, C = x2d.shape
