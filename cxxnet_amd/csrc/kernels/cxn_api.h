@@ -105,7 +105,7 @@ CXN_API int cxn_conv_rowrun_fwd2(const void *x, const void *w, const float *bias
 CXN_API int cxn_conv_fewc_fwd(const void *x, const void *w, const float *bias, void *y, int N, int H, int W, int Ho,
                               int Wo, int Cout, int KH, int KW, int S, int P, int ldc, int relu, void *stream);
 
-// nn_kernels.hip
+// layout_kernels.hip
 CXN_API int cxn_nchw_f32_to_nhwc_bf16(const float *x, void *y, int N, int C, int H, int W, int Cp, int Wp,
                                       float scale, void *stream);
 CXN_API int cxn_image_u8_to_nhwc_bf16(const void *pix, const int *prm, const float *cm, const float *mean, int B,
@@ -116,7 +116,8 @@ CXN_API int cxn_nhwc_bf16_to_nchw_f32(const void *x, float *y, int N, int C, int
 CXN_API int cxn_transpose(const void *x, void *y, int B, int R, int Cc, void *stream);
 CXN_API int cxn_conv_weight_flip(const void *w, void *wt, int G, int Co, int KH, int KW, int Ci, void *stream);
 CXN_API int cxn_conv_weight_flip_multi(const void *const *ws, void *const *wts, const int *dims, int n, void *stream);
-CXN_API int cxn_set_kernel_variant(int which, int v);
+
+// pool_kernels.hip
 CXN_API int cxn_pool_fwd(const void *x, void *y, void *arg, int N, int H, int W, int C, int Ho, int Wo, int KH,
                          int KW, int S, int P, int mode, int relu, void *stream);
 CXN_API int cxn_pool_bwd_tie_all(const void *x, const void *y, const void *dy, void *dx, int N, int H, int W, int C,
@@ -124,6 +125,8 @@ CXN_API int cxn_pool_bwd_tie_all(const void *x, const void *y, const void *dy, v
 CXN_API int cxn_pool_bwd(const void *x, const void *arg, const void *dy, void *dx, int N, int H, int W, int C,
                          int Ho, int Wo, int KH, int KW, int S, int P, int mode, int relu, float *db, float *ws,
                          long ws_elems, void *stream);
+
+// lrn_kernels.hip
 CXN_API int cxn_lrn_fwd(const void *x, void *y, long npix, int C, int nsize, float alpha, float beta, float knorm,
                         void *stream);
 CXN_API int cxn_pool_lrn_fwd(const void *x, void *P, void *arg, void *Y, int N, int Hin, int Win, int C, int Ho,
@@ -136,24 +139,33 @@ CXN_API int cxn_lrn_bwd_db(const void *x, const void *dy, void *dx, long npix, i
                            void *stream);
 CXN_API int cxn_lrn_bwd(const void *x, const void *dy, void *dx, long npix, int C, int nsize, float alpha,
                         float beta, float knorm, int mask_relu, void *stream);
+
+// act_kernels.hip
 CXN_API int cxn_act_fwd(const void *x, void *y, void *y2, long n, int kind, float b, void *stream);
 CXN_API int cxn_act_bwd(const void *y, const void *dy, void *dx, long n, int kind, float b, void *stream);
 CXN_API int cxn_dropout(const void *x, void *y, long n, unsigned seed, const int *counter, float pkeep, void *stream);
+
+// loss_kernels.hip
 CXN_API int cxn_metric_eval(const float *p, int ldp, const float *lab, int ldl, int lw, int B, int K, int nm,
                             const int *kinds, const int *args, double *acc, float *part, void *stream);
 CXN_API int cxn_softmax(const void *x, void *y, float *pf, int rows, int K, void *stream);
 CXN_API int cxn_loss_grad(const float *p32, void *node, const float *label, int rows, int K, int lw, float scale,
                           int kind, void *stream);
+
+// reduce_kernels.hip
 CXN_API int cxn_colsum(const void *dy, float *db, long rows, int C, float *ws, long ws_elems, void *stream);
 CXN_API int cxn_colsum_multi(const void *const *dys, float *const *dbs, const long *rows, const int *Cs,
                              const void *const *masks, int n, void *stream, const long *lds);
 CXN_API int cxn_set_deterministic(int on);
+CXN_API int cxn_set_kernel_variant(int which, int v);
 CXN_API int cxn_splitk_accumulate(const float *ws, int nsplit, long slab, float *out, void *stream);
 CXN_API int cxn_splitk_finalize(const float *ws, int nsplit, long slab, void *out, long rows, int cols,
                                 const float *bias, int relu, int mask_relu, void *stream);
 CXN_API int cxn_splitk_finalize_dropout(const float *ws, int nsplit, long slab, void *out, long rows, int cols,
                                         const float *bias, int relu, unsigned seed, const int *counter, float pkeep,
                                         void *stream);
+
+// copy_kernels.hip
 CXN_API int cxn_cast_f32_bf16(const float *x, void *y, long n, void *stream);
 CXN_API int cxn_add_bf16(const void *a, const void *b, void *y, long n, void *stream);
 CXN_API int cxn_fanout_bf16(const void *src, void *d0, void *d1, void *d2, void *d3, int nd, long n, void *stream);

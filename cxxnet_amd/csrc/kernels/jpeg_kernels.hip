@@ -1,6 +1,6 @@
 // GPU half of the JPEG decode stage: dequantise + islow IDCT of every staged coefficient block,
 // then fancy chroma upsampling + YCbCr->RGB + crop + mirror into the uint8 batch the image
-// kernel (nn_kernels.hip image_u8_*) turns into the network input.
+// kernel (layout_kernels.hip image_u8_*) turns into the network input.
 //
 // Reference behaviour: src/utils/decoder.h:21-104 (libjpeg decode of one record to RGB) and the
 // crop / mirror of src/io/iter_augment_proc-inl.hpp:98-162.  The host (runtime/jpeg_decode.h

@@ -1,5 +1,6 @@
 """Memory-bound layer ops (pooling, LRN, activations, dropout, softmax/loss,
-layout conversion, bias gradient).  GPU: csrc/kernels/nn_kernels.hip; CPU: fp32 torch.
+layout conversion, bias gradient).  GPU: one file per family, csrc/kernels/{pool,lrn,act,loss,layout,reduce,copy}_kernels.hip;
+CPU: fp32 torch.
 
 All activations are NHWC (see ops/gemm.py for the layout contract).
 """
@@ -452,7 +453,7 @@ def pool_backward_tie_all(x, y, dy, dx, KH, KW, S, P, relu=False):
 # ----------------------------------------------------------------------------- LRN
 def _lrn_window_sum(v, nsize):
     """Sum over channels c - h .. c + h (h = nsize // 2) clipped to [0, C): the window of the
-    kernels (nn_kernels.hip) and of the reference's chpool, which centres 2 h + 1 channels on c;
+    kernels (lrn_kernels.hip) and of the reference's chpool, which centres 2 h + 1 channels on c;
     for an even local_size that is one channel more than nsize."""
     C = v.shape[-1]
     half = nsize // 2

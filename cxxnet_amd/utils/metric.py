@@ -99,7 +99,7 @@ class DeviceMetricSet:
 
     def _run_kernel(self, lo, hi, p, lab, b):
         """metrics lo..hi-1 share scores p and labels lab: one metric_rows + one
-        metric_accum launch (csrc/kernels/nn_kernels.hip) add their sums into the float64
+        metric_accum launch (csrc/kernels/loss_kernels.hip) add their sums into the float64
         accumulator."""
         import ctypes
         from .. import native

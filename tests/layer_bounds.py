@@ -1,6 +1,6 @@
 """Float64 references and derived per-element error bounds for the kernels of the layer
 `batch_norm` (and `bias`), prelu, insanity, insanity_max_pooling (csrc/kernels/layer_kernels.hip),
-the activations and dropout (csrc/kernels/nn_kernels.hip) and the fused optimizer step
+the activations and dropout (csrc/kernels/act_kernels.hip) and the fused optimizer step
 (csrc/kernels/optim_kernels.hip), in the style of tests/bounds.py and tests/bn_bounds.py: the
 operands are the exact bf16 / fp32 values the kernel reads, the reference is float64 on the CPU and
 written out here (it never calls the package's host path of the same op; only the package's counter

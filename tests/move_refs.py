@@ -1,6 +1,6 @@
 """References, case lists and guards for the kernels that move data between the layers
-(csrc/kernels/nn_kernels.hip: transposes, weight flip, concat, channel copies, pads, casts, split
-forward / backward, layout conversion, the image input stage) and for the column sums that are
+(csrc/kernels/copy_kernels.hip, layout_kernels.hip and reduce_kernels.hip: transposes, weight
+flip, concat, channel copies, pads, casts, split forward / backward, layout conversion, the image input stage) and for the column sums that are
 every bias gradient.  Everything here runs on the CPU and is written with explicit index
 arithmetic, independent of cxxnet_amd.ops and of U8Images.to_float.
 

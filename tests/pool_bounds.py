@@ -1,5 +1,5 @@
 """Float64 references, derived per-element bounds and the shared case table of the pooling kernels
-(csrc/kernels/nn_kernels.hip behind cxn_pool_fwd, cxn_pool_bwd and cxn_pool_bwd_tie_all).
+(csrc/kernels/pool_kernels.hip behind cxn_pool_fwd, cxn_pool_bwd and cxn_pool_bwd_tie_all).
 
 The references are written out as loops over the KH * KW taps with slicing, the way
 bounds.pool3s2_first_max and bounds._route are for 3 x 3 / 2; they share no code with the

@@ -1,5 +1,5 @@
 """prelu, insanity, insanity_max_pooling (csrc/kernels/layer_kernels.hip), the activations and dropout
-(csrc/kernels/nn_kernels.hip) element by element against the float64 references and the derived
+(csrc/kernels/act_kernels.hip) element by element against the float64 references and the derived
 bounds of tests/layer_bounds.py, through the ops layer as the layers call them.  The random draws
 are the package's counter hash (the generator); the operations are written out in the reference.
 Every output is the head of a sentinel-filled buffer; nothing behind it may change.

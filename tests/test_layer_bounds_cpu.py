@@ -332,7 +332,7 @@ def test_dropout_emulation_and_defect(n, pkeep):
     x = LC.dropout_inputs(n)
     ctr = torch.tensor([LC.DROPOUT_COUNTER], dtype=torch.int32)
     ref, bound, keep = LB.dropout_ref(x, pkeep, LC.DROPOUT_SEED, ctr)
-    t = float(f32(pkeep)) * 4294967296.0  # dropout_thresh of nn_kernels.hip
+    t = float(f32(pkeep)) * 4294967296.0  # dropout_thresh of nn_shared.h
     thresh = 0xFFFFFFFF if t >= 4294967295.0 else int(t)
     h = LB._hash_u32(torch.arange(n, dtype=torch.int64), LB.effective_seed(LC.DROPOUT_SEED, ctr)).numpy()
 

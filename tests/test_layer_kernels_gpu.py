@@ -1,6 +1,6 @@
 """GPU kernels of batch_norm, prelu, insanity, insanity_max_pooling, bias, split, concat
-(csrc/kernels/layer_kernels.hip, nn_kernels.hip) against the CPU executor's fp32 torch
-formulas.  Random draws use the same counter hash on both devices, so even the
+(csrc/kernels/layer_kernels.hip, pool_kernels.hip, copy_kernels.hip, reduce_kernels.hip) against
+the CPU executor's fp32 torch formulas.  Random draws use the same counter hash on both devices, so even the
 training-mode (noisy) paths compare element by element.  Inputs are bf16-representable,
 so max-pool winners agree exactly."""
 import pytest

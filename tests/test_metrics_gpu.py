@@ -1,4 +1,4 @@
-"""The fused metric kernel (metric_rows / metric_accum, csrc/kernels/nn_kernels.hip) against
+"""The fused metric kernel (metric_rows / metric_accum, csrc/kernels/loss_kernels.hip) against
 the torch formulation of the same metrics and the native host metrics."""
 import numpy as np
 import pytest

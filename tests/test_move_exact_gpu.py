@@ -1,4 +1,4 @@
-"""The kernels that move data between the layers (csrc/kernels/nn_kernels.hip), bit for bit against
+"""The kernels that move data between the layers (csrc/kernels/copy_kernels.hip, layout_kernels.hip, reduce_kernels.hip), bit for bit against
 the explicit-index references of tests/move_refs.py: both transposes, the weight flip (single and
 multi), concat forward / backward, channel_copy and channel_copy8 in their three modes,
 pad_interior (both widths), pad_rows, add_rows_f32, fanout, sum_bf16 (aliased, relu'-masked,

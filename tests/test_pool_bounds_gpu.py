@@ -1,4 +1,4 @@
-"""The pooling kernels (csrc/kernels/nn_kernels.hip behind cxn_pool_fwd, cxn_pool_bwd and
+"""The pooling kernels (csrc/kernels/pool_kernels.hip behind cxn_pool_fwd, cxn_pool_bwd and
 cxn_pool_bwd_tie_all) per element against the float64 references of tests/pool_bounds.py, on its
 case table: max outputs and first-max offsets exactly, sum / avg outputs and every data gradient
 within the derived bound, the folded bias gradient against bounds.dbias_ref of the dx the kernel
