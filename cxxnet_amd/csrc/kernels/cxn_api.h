@@ -211,6 +211,14 @@ CXN_API int cxn_bn_ma_fwd_infer(const void *x, void *y, const float *slope, cons
 CXN_API int cxn_bn_ma_bwd(const void *g, const void *x, void *dx, const float *slope, float *gslope, float *gbias,
                           const float *stat, float *coef, float *ws, long ws_floats, long rows, int C, void *stream);
 
+// gn_kernels.hip
+CXN_API long cxn_gn_ws_floats(long B, long HW, int C);
+CXN_API int cxn_gn_fwd(const void *x, void *y, const float *slope, const float *bias, float *mean, float *rstd,
+                       float *ws, long ws_floats, long B, long HW, int C, int groups, float eps, void *stream);
+CXN_API int cxn_gn_bwd(const void *g, const void *x, void *dx, const float *slope, float *gslope, float *gbias,
+                       const float *mean, const float *rstd, float *coef, float *ws, long ws_floats, long B, long HW,
+                       int C, int groups, void *stream);
+
 // add_kernels.hip
 CXN_API int cxn_add_fwd(const void *x0, const void *x1, const void *x2, const void *x3, int n_in, void *y,
                         void *mask, long n, int relu, void *stream);

@@ -46,6 +46,7 @@ enum : int {
   kRelu6 = 43,
   kHSigmoid = 44,
   kHSwish = 45,
+  kGroupNorm = 46,
   kPairTestGap = 1024,
 };
 
@@ -66,6 +67,7 @@ inline int GetLayerType(const std::string &t) {
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
       {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
+      {"group_norm", kGroupNorm},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

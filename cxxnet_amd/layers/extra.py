@@ -1,11 +1,12 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
-ch_scale and relu6 / hsigmoid / hswish.
+ch_scale, relu6 / hsigmoid / hswish and group_norm.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
 csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, ch_scale in
-csrc/kernels/se_kernels.hip, relu6 / hsigmoid / hswish in csrc/kernels/hact_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
+csrc/kernels/se_kernels.hip, relu6 / hsigmoid / hswish in csrc/kernels/hact_kernels.hip, group_norm in
+csrc/kernels/gn_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
 from __future__ import annotations
@@ -496,6 +497,100 @@ class HardActLayer(Layer):
             L.hact_backward(self.kind, nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
 
 
+class GroupNormLayer(Layer):
+    """`group_norm` (type id 46) -- an extension, no reference counterpart: group normalisation
+    (Wu and He, 2018), 1 -> 1, the output shaped like the input.  The node is read as
+    [B][HW][C] (a feature map in NHWC; a matrix node has HW = 1 and C = its features) and every
+    sample is normalised on its own over `gn_group` groups of Cg = C / gn_group consecutive
+    channels: with mean and the biased var over the HW Cg elements of a (sample, group),
+    rstd = (var + eps)^-1/2 and y = (x - mean) rstd slope[c] + bias[c], fp32 arithmetic and one
+    rounding to the node's dtype.  is_train does not enter: training and inference compute the
+    same thing, a row's output does not depend on its batch neighbours, and there is no running
+    state -- nothing for NeuralNet._build_bn_state, nothing a data-parallel step has to send.
+    gn_group = 1 is layer normalisation, gn_group = C instance normalisation.
+        gn_group    groups, default 32; an integer >= 1 that divides C (not `ngroup`, the conv
+                    key, which a global setting would otherwise hand to this layer)
+        eps         default 1e-5;   init_slope default 1;   init_bias default 0
+    Backward, with g the gradient held by the output node, xhat = (x - mean) rstd, m = HW Cg:
+    gbias[c] += sum g, gslope[c] += sum g xhat over the batch and the map, and with prop_grad
+    dx = rstd (slope[c] g - s1 / m - xhat s2 / m) into x.gdst, s1 / s2 the sums of slope g and
+    slope g xhat over the (sample, group).  x is read from the input node again, so the output
+    node must differ from the input; x.gdst may be x.data or the output node's buffer.  slope
+    ("wmat") and bias ("bias") are arena parameters; the checkpoint holds slope, bias."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "group_norm"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.init_slope = 1.0
+        self.init_bias = 0.0
+        self.eps = 1e-5
+        self.gn_group = "32"
+        self._st = None
+        self.loaded = None
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "init_slope":
+            self.init_slope = float(val)
+        elif name == "init_bias":
+            self.init_bias = float(val)
+        elif name == "eps":
+            self.eps = float(val)
+        elif name == "gn_group":
+            self.gn_group = val  # checked against the channels in init_connection
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "GroupNormLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "GroupNormLayer: group_norm reads its input again in backward, so the output node must differ from "
+               "the input (no self-loop)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "GroupNormLayer: padded-channel input is not supported")
+        nodes_out[0].set_shape(*nodes_in[0].shape)
+        self.channel = _num_feat(nodes_in[0])
+        try:
+            self.groups = int(str(self.gn_group).strip())
+        except ValueError:
+            self.groups = 0
+        _check(self.groups >= 1 and self.channel % self.groups == 0,
+               "GroupNormLayer: gn_group = %s must be an integer >= 1 that divides the %d channels"
+               % (str(self.gn_group).strip(), self.channel))
+        b, c, h, w = nodes_in[0].shape
+        self.max_batch = b
+        self.hw = c * h * w // self.channel
+        self.params = [ParamSpec("wmat", (self.channel,), _bias_init(self.init_slope)),
+                       ParamSpec("bias", (self.channel,), _bias_init(self.init_bias))]
+
+    def _view(self, t):
+        return t.view(-1, self.hw, self.channel)
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.GNState(self.max_batch, self.hw, self.channel, self.groups, x.device)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = self._view(nodes_in[0].data)
+        L.gn_forward(x, self._view(nodes_out[0].data), self.params[0].w, self.params[1].w, self.eps, self._state(x))
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        g = self._view(nodes_out[0].data)
+        L.gn_backward(g, self._view(nodes_in[0].data), self._view(nodes_in[0].gdst), self.params[0].w,
+                      self.params[0].g, self.params[1].g, self._state(g), prop_grad)
+
+    def save_model(self, fo: BinWriter):
+        fo.write_tensor(self.params[0].w)
+        fo.write_tensor(self.params[1].w)
+
+    def load_model(self, fi: BinReader):
+        self.loaded = [fi.read_tensor(1), fi.read_tensor(1)]
+
+    def loaded_values(self):
+        return self.loaded
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -811,6 +906,7 @@ def _register():
     register(43, lambda ctx: HardActLayer(ctx, "relu6"))
     register(44, lambda ctx: HardActLayer(ctx, "hsigmoid"))
     register(45, lambda ctx: HardActLayer(ctx, "hswish"))
+    register(46, GroupNormLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -1,4 +1,5 @@
-"""Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling.
+"""Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
+extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -202,6 +203,85 @@ def bn_ma_backward(g2d, x2d, dx2d, slope, gslope, gbias, st: BNMAState, prop_gra
                                     slope.data_ptr(), gslope.data_ptr(), gbias.data_ptr(), st.stat.data_ptr(),
                                     st.coef.data_ptr(), st.ws.data_ptr(), st.ws.numel(), rows, C, _stream()),
                  "bn_ma_bwd")
+
+
+# ----------------------------------------------------------------------------- group norm
+class GNState:
+    """Per-layer device buffers of group_norm, sized once for max_batch: mean and rstd [B][groups]
+    of the last forward, the backward's per-group coefficients (s1 / m, s2 / m), and the partial
+    workspace of the fixed-order reductions (csrc/kernels/gn_kernels.hip).  A smaller batch uses
+    their leading rows."""
+
+    def __init__(self, max_batch, HW, C, groups, device):
+        self.groups = int(groups)
+        self.mean = torch.zeros(max_batch, groups, dtype=torch.float32, device=device)
+        self.rstd = torch.zeros(max_batch, groups, dtype=torch.float32, device=device)
+        self.coef = torch.zeros(max_batch, groups, 2, dtype=torch.float32, device=device)
+        self.ws = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_gn_ws_floats(int(max_batch), int(HW), int(C)))
+            self.ws = torch.zeros(max(n, 1), dtype=torch.float32, device=device)
+
+
+def _gn_dims(x, st, who):
+    B, HW, C = x.shape
+    if C % st.groups != 0 or B > st.mean.shape[0]:
+        raise ValueError("%s: x [B][HW][C] with C a multiple of the %d groups and B <= %d expected, not %s"
+                         % (who, st.groups, st.mean.shape[0], tuple(x.shape)))
+    return B, HW, C, st.groups
+
+
+def gn_forward(x, y, slope, bias, eps, st: GNState):
+    """x, y [B][HW][C].  Per sample b and group g (channels [g Cg, (g + 1) Cg), m = HW Cg
+    elements): mean, biased var, rstd = (var + eps)^-1/2 into st.mean / st.rstd [b][g], and
+    y = (x - mean) rstd slope[c] + bias[c].  The same in training and inference.  y must not
+    alias x."""
+    B, HW, C, G = _gn_dims(x, st, "gn_forward")
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("gn_forward: y must not alias x (backward reads x again)")
+    if not _native_t(x):
+        xg = x.float().reshape(B, HW, G, C // G)
+        mean = xg.mean((1, 3), keepdim=True)
+        d = xg - mean
+        var = (d * d).mean((1, 3), keepdim=True)
+        rstd = 1.0 / torch.sqrt(var + eps)
+        st.mean[:B].copy_(mean.reshape(B, G))
+        st.rstd[:B].copy_(rstd.reshape(B, G))
+        y.copy_((d * rstd).reshape(B, HW, C) * slope + bias)
+        return
+    _flat_bf16(x, y, who="gn_forward")
+    native.check(_k().cxn_gn_fwd(x.data_ptr(), y.data_ptr(), slope.data_ptr(), bias.data_ptr(), st.mean.data_ptr(),
+                                 st.rstd.data_ptr(), st.ws.data_ptr(), st.ws.numel(), B, HW, C, G, float(eps),
+                                 _stream()), "gn_fwd")
+
+
+def gn_backward(g, x, dx, slope, gslope, gbias, st: GNState, prop_grad: bool):
+    """With xhat = (x - mean) rstd of the last forward: gbias[c] += sum g, gslope[c] += sum g xhat
+    (over the batch and the map), and with prop_grad dx = rstd (slope[c] g - s1 / m - xhat s2 / m),
+    s1 = sum slope g and s2 = sum slope g xhat over the m elements of the (sample, group).  dx may
+    alias x or g; without prop_grad it is not written."""
+    B, HW, C, G = _gn_dims(g, st, "gn_backward")
+    if not _native_t(g):
+        Cg = C // G
+        mean, rstd = st.mean[:B].reshape(B, 1, G, 1), st.rstd[:B].reshape(B, 1, G, 1)
+        g32 = g.float().reshape(B, HW, G, Cg)
+        xh = (x.float().reshape(B, HW, G, Cg) - mean) * rstd
+        gbias.add_(g32.sum((0, 1)).reshape(C))
+        gslope.add_((g32 * xh).sum((0, 1)).reshape(C))
+        if prop_grad:
+            sg = g32 * slope.reshape(G, Cg)
+            m = float(HW * Cg)
+            s1 = sg.sum((1, 3), keepdim=True)
+            s2 = (sg * xh).sum((1, 3), keepdim=True)
+            dx.copy_((rstd * (sg - s1 / m - xh * s2 / m)).reshape(B, HW, C))
+        return
+    _flat_bf16(g, x, who="gn_backward")
+    if prop_grad:
+        _flat_bf16(dx, who="gn_backward")
+    native.check(_k().cxn_gn_bwd(g.data_ptr(), x.data_ptr(), dx.data_ptr() if prop_grad else None, slope.data_ptr(),
+                                 gslope.data_ptr(), gbias.data_ptr(), st.mean.data_ptr(), st.rstd.data_ptr(),
+                                 st.coef.data_ptr(), st.ws.data_ptr(), st.ws.numel(), B, HW, C, G, _stream()),
+                 "gn_bwd")
 
 
 # ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
