@@ -230,6 +230,15 @@ CXN_API long cxn_hact_pass_elems();
 CXN_API int cxn_hact_fwd(const void *x, void *y, long n, int kind, void *stream);
 CXN_API int cxn_hact_bwd(const void *x, const void *g, void *dx, long n, int kind, void *stream);
 
+// silu_kernels.hip
+CXN_API long cxn_silu_pass_elems();
+CXN_API int cxn_silu_fwd(const void *x, void *y, long n, void *stream);
+CXN_API int cxn_silu_bwd(const void *x, const void *g, void *dx, long n, void *stream);
+
+// droppath_kernels.hip
+CXN_API long cxn_drop_path_pass_elems();
+CXN_API int cxn_drop_path(void *x, long B, long n, unsigned seed, const int *counter, float pkeep, void *stream);
+
 // se_kernels.hip
 CXN_API int cxn_se_parts(long B, long HW, int C);
 CXN_API long cxn_se_ws_floats(long Bmax, long HW, int C);

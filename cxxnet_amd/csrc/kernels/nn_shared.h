@@ -1,5 +1,6 @@
 // What the memory-bound layer-family files share (layout_, pool_, lrn_, act_, loss_, reduce_ and
-// copy_kernels.hip; nothing else includes this): the block size and grid-stride index of their
+// copy_kernels.hip, and droppath_kernels.hip for dropout's threshold; nothing else includes this):
+// the block size and grid-stride index of their
 // kernels, the runtime value -> template argument dispatchers of their launchers, and the few
 // host-side pieces one family's launchers need of another's.  No kernel lives here: a __global__
 // function in a header would be emitted once per including file.

@@ -47,6 +47,8 @@ enum : int {
   kHSigmoid = 44,
   kHSwish = 45,
   kGroupNorm = 46,
+  kSilu = 47,
+  kDropPath = 48,
   kPairTestGap = 1024,
 };
 
@@ -67,7 +69,7 @@ inline int GetLayerType(const std::string &t) {
       {"ch_concat", kChConcat}, {"prelu", kPRelu}, {"batch_norm", kBatchNorm},
       {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
-      {"group_norm", kGroupNorm},
+      {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,12 +1,13 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
-ch_scale, relu6 / hsigmoid / hswish and group_norm.
+ch_scale, relu6 / hsigmoid / hswish, group_norm, silu and drop_path.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
 csrc/kernels/bn_ma_kernels.hip, add in csrc/kernels/add_kernels.hip, ch_scale in
 csrc/kernels/se_kernels.hip, relu6 / hsigmoid / hswish in csrc/kernels/hact_kernels.hip, group_norm in
-csrc/kernels/gn_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
+csrc/kernels/gn_kernels.hip, silu in csrc/kernels/silu_kernels.hip, drop_path in
+csrc/kernels/droppath_kernels.hip, concat / split / bias on the channel-copy / add / column-sum kernels, fixconn on the MFMA GEMM.  The CPU
 executor runs the same formulas in fp32 torch with the same counter-hash random draws.
 """
 from __future__ import annotations
@@ -497,6 +498,90 @@ class HardActLayer(Layer):
             L.hact_backward(self.kind, nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
 
 
+class SiluLayer(Layer):
+    """`silu` (type id 47) -- an extension, no reference counterpart: y = x sigma(x) with
+    sigma(x) = 1 / (1 + e^-x), the activation of the EfficientNets, 1 -> 1 on nodes of any shape.
+    fp32 arithmetic, one rounding to the node's dtype; sigma is formed as 1 / (1 + e^-x), so both
+    ends stay finite: y = -0 where e^-x overflows, y = x (the same bits) where sigma rounds to 1.
+    Backward takes the derivative from the INPUT node (silu is not monotonic, so its output cannot
+    stand in for x): with g the gradient held by the output node,
+    dx = g sigma(x) (1 + x (1 - sigma(x))) goes to x.gdst, which may be x.data.  So the layer never
+    writes its input in forward and reads it again in backward: the output node must differ from
+    the input node.  The output is not claimed non-negative.  No parameters and no state: the
+    checkpoint holds nothing for it."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "silu"
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "SiluLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "SiluLayer: silu reads its input again in backward, so the output node must differ from the input "
+               "(no self-loop)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "SiluLayer: padded-channel input is not supported")
+        nodes_out[0].set_shape(*nodes_in[0].shape)
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        L.silu_forward(nodes_in[0].data, nodes_out[0].data)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if prop_grad:
+            L.silu_backward(nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
+
+
+class DropPathLayer(Layer):
+    """`drop_path` (type id 48) -- an extension, no reference counterpart: stochastic depth per
+    sample (Huang et al. 2016, as the EfficientNets use it), a self-loop on the residual branch in
+    front of an `add`: `layer[a->a] = drop_path`.  The node is read as [B][n], n the elements of
+    one sample.  In training with drop_prob > 0, pkeep = 1 - drop_prob, sample b is kept iff
+    hash_u32(b, seed') < dropout_thresh(pkeep), seed' = hash_u32(step counter, layer seed) --
+    `dropout`'s mask at element b; a kept sample becomes x (1.0f / pkeep), one fp32 product and one
+    rounding to the node's dtype, a dropped one +0 whatever it held (a selection, not x 0).
+    Backward applies the same operation, with the same counter value, to the gradient the node
+    holds.  With is_train false or drop_prob = 0 nothing is launched.
+        drop_prob   in [0, 1), default 0 (not `threshold`, the dropout key, which a global setting
+                    would otherwise hand to this layer as well)
+    b is the row of the tensor this process holds, as dropout's element index is: under data
+    parallelism every rank draws the same stream for its own rows; a rank-dependent stream is out
+    of scope.  No parameters and no state: the checkpoint holds nothing for it."""
+    # the kernel is a library launch with step-invariant arguments (the counter is read on the
+    # device; HIP graphs replay it); the launch-list audit (tests/test_launch_hygiene_gpu.py's
+    # all-layer net) does not cover it
+    replay_audited = False
+    type_name = "drop_path"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.drop_prob = 0.0
+        self.seed = int(torch.randint(0, 2**31 - 1, (1,), generator=ctx.gen).item())
+        self._train = True
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "drop_prob":
+            self.drop_prob = float(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "DropPathLayer: only support 1-1 connection")
+        _check(nodes_in[0] is nodes_out[0], "DropPathLayer is a self-loop Layer")
+        _check(0.0 <= self.drop_prob < 1.0, "DropPathLayer: drop_prob must be in [0, 1)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "DropPathLayer: padded-channel node is not supported")
+
+    def _apply(self, node):
+        # (a layer outside a net has no step counter: the layer seed alone)
+        L.drop_path_apply(node.data, self.seed, 1.0 - self.drop_prob, getattr(self.ctx, "step_counter", None))
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        self._train = is_train
+        if is_train and self.drop_prob > 0:
+            self._apply(nodes_in[0])
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if self._train and self.drop_prob > 0:
+            self._apply(nodes_in[0])
+
+
 class GroupNormLayer(Layer):
     """`group_norm` (type id 46) -- an extension, no reference counterpart: group normalisation
     (Wu and He, 2018), 1 -> 1, the output shaped like the input.  The node is read as
@@ -907,6 +992,8 @@ def _register():
     register(44, lambda ctx: HardActLayer(ctx, "hsigmoid"))
     register(45, lambda ctx: HardActLayer(ctx, "hswish"))
     register(46, GroupNormLayer)
+    register(47, SiluLayer)
+    register(48, DropPathLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -1,5 +1,6 @@
 """Model zoo: .conf network definitions (AlexNet, GoogLeNet/Inception-v1, VGG-16, ResNet-18,
-ResNet-18-GN (group_norm in place of batch_norm_ma), SE-ResNet-18, MobileNet-v1, MobileNet-v3-Large, MNIST MLP/conv, Kaggle-bowl convnet) and helpers
+ResNet-18-GN (group_norm in place of batch_norm_ma), SE-ResNet-18, MobileNet-v1, MobileNet-v3-Large,
+EfficientNet-B0 (silu, drop_path), MNIST MLP/conv, Kaggle-bowl convnet) and helpers
 to load them."""
 from __future__ import annotations
 

@@ -37,6 +37,7 @@ K_SPLIT, K_CONCAT, K_CHCONCAT, K_SUMPOOL, K_AVGPOOL, K_LRN = 23, 18, 28, 12, 13,
 K_RELU_MAXPOOL = 21
 K_ADD = 41  # extension (layers/extra.py AddLayer)
 K_CH_SCALE = 42  # extension (layers/extra.py ChScaleLayer)
+K_DROP_PATH = 48  # extension (layers/extra.py DropPathLayer): a self-loop that writes its node, as dropout is
 # queued bias-gradient bytes (dy read by the column sums) that trigger a side-stream launch
 _BIAS_FLUSH_BYTES = int(float(os.environ.get("CXXNET_BIAS_FLUSH_MB", "16")) * (1 << 20))
 # layers that only READ their input node in forward and write the input gradient through
@@ -174,6 +175,7 @@ class NeuralNet:
             cons = consumers.get(id(b), [])
             real = [(j, sl) for j, sl in cons if not sl]
             loops = [j for j, sl in cons if sl]
+            # (a drop_path self-loop on b is a writer the fused consumers do not know: no fusion)
             if len(real) != 1 or any(self.connections[j].type != K_DROPOUT for j in loops):
                 continue
             j = real[0][0]
@@ -207,7 +209,8 @@ class NeuralNet:
 
     def _mark_nonneg(self):
         """Nodes that can only hold values >= 0 (relu outputs -- fused into their producer or
-        not -- and what max-pool / LRN / dropout / split / concat make of them); a max-pool
+        not -- and what max-pool / LRN / dropout / drop_path / split / concat make of them: a kept
+        sample is scaled by 1 / pkeep > 0, a dropped one is +0); a max-pool
         reading one gets input_nonneg, and its kernels then take the window maximum on integer
         keys of the bf16 bits (ops.pool_forward(nonneg=True))."""
         nn = set()
@@ -221,7 +224,7 @@ class NeuralNet:
             elif t in (K_MAXPOOL, K_RELU_MAXPOOL):
                 ok = t == K_RELU_MAXPOOL or bool(getattr(lay, "relu", False)) or all(id(n) in nn for n in ins)
                 lay.input_nonneg = all(id(n) in nn for n in ins)
-            elif t in (K_LRN, K_DROPOUT, K_SPLIT, K_CHCONCAT, K_CONCAT):
+            elif t in (K_LRN, K_DROPOUT, K_DROP_PATH, K_SPLIT, K_CHCONCAT, K_CONCAT):
                 ok = all(id(n) in nn for n in ins)
             else:
                 ok = False
@@ -424,7 +427,10 @@ class NeuralNet:
         writes their gradients through gdst, so the identity branch of a residual block aliases
         the block input.  So does a `ch_scale` for its first input, the feature map, which it only
         reads (forward and backward; the split's sum overwrites the shared buffer after every
-        consumer's backprop); a split output used as its gate keeps the copying split."""
+        consumer's backprop); a split output used as its gate keeps the copying split.  A
+        self-loop on an output (dropout, drop_path) WRITES that node: such an output has the loop
+        among its consumers, so the split keeps its copies and the sibling outputs and the input
+        are untouched."""
         self.split_alias = {}
         for i, conn in enumerate(self.connections):
             if conn.type != K_SPLIT or conn.shared or len(conn.nodes_in) != 1:

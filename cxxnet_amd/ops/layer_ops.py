@@ -1,5 +1,5 @@
 """Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
-extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish.
+extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -468,6 +468,91 @@ def hact_backward(kind: str, x, g, dx):
         return
     _flat_bf16(x, g, dx, who="hact")
     native.check(_k().cxn_hact_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), k, _stream()), "hact_bwd")
+
+
+# ----------------------------------------------------------------------------- silu
+def silu_pass_elems() -> int:
+    """Elements one pass of the silu kernels' capped grid covers; a larger tensor makes a thread take
+    a second grid-stride trip."""
+    return int(_k().cxn_silu_pass_elems())
+
+
+def _sigma32(v):
+    """1 / (1 + e^-x) in fp32, in the kernels' formulation: finite at both ends (e^-x = inf gives +0,
+    e^-x = 0 gives 1 exactly)"""
+    return 1.0 / (1.0 + torch.exp(-v))
+
+
+def silu_forward(x, y):
+    """y = x sigma(x), sigma(x) = 1 / (1 + e^-x), in fp32, one rounding to y's dtype.  Where sigma
+    rounds to 1 (x >= 17 or so) y is x, the same bits; where e^-x overflows y is -0.
+    y must not alias x."""
+    if x.numel() != y.numel():
+        raise ValueError("silu: x and y of one size expected")
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("silu: y must not alias x (backward reads x again)")
+    if not _native_t(x):
+        v = x.float()
+        y.copy_((v * _sigma32(v)).view(y.shape))
+        return
+    _flat_bf16(x, y, who="silu")
+    native.check(_k().cxn_silu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "silu_fwd")
+
+
+def silu_backward(x, g, dx):
+    """dx = g sigma(x) (1 + x (1 - sigma(x))), the derivative taken from the layer's INPUT x, in
+    fp32, one rounding.  Where sigma rounds to 1 dx is g, the same bits; where e^-x overflows dx is
+    a zero.  dx may alias x; it must not alias g."""
+    if not x.numel() == g.numel() == dx.numel():
+        raise ValueError("silu: x, g and dx of one size expected")
+    if dx.data_ptr() == g.data_ptr():
+        raise ValueError("silu: dx must not alias g (it may alias x)")
+    if not _native_t(g):
+        v, gv = x.float(), g.float().view(x.shape)
+        s = _sigma32(v)
+        dx.copy_((gv * s * (1.0 + v * (1.0 - s))).view(dx.shape))
+        return
+    _flat_bf16(x, g, dx, who="silu")
+    native.check(_k().cxn_silu_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), _stream()), "silu_bwd")
+
+
+# ----------------------------------------------------------------------------- drop_path (per-sample dropout)
+def drop_path_pass_elems() -> int:
+    """Elements of one sample that a pass of the drop_path kernel's capped grid covers."""
+    return int(_k().cxn_drop_path_pass_elems())
+
+
+def drop_path_keep_ref(B: int, seed: int, pkeep: float, device="cpu") -> torch.Tensor:
+    """The kernel's keep decisions as a bool tensor of B: hash_u32(b, seed) < dropout_thresh(pkeep)
+    (csrc/kernels/nn_shared.h), seed the EFFECTIVE seed (ops.nn.effective_seed).  This is dropout's
+    mask at element b, with the threshold taken from pkeep as the fp32 number the kernel receives."""
+    p32 = float(torch.tensor(pkeep, dtype=torch.float32))
+    t = min(int(p32 * 4294967296.0), 0xFFFFFFFF)
+    return _hash_u32(torch.arange(B, dtype=torch.int64, device=device), seed & 0xFFFFFFFF) < t
+
+
+def drop_path_apply(x, seed: int, pkeep: float, counter=None):
+    """x[B][...] in place: sample b is kept or dropped as a whole (drop_path_keep_ref with the seed
+    hash(counter, seed), read on the device, so a captured HIP graph draws a new mask on every
+    replay).  A kept sample becomes x * (1.0f / pkeep), one fp32 product and one rounding to x's
+    dtype; a dropped one becomes +0 whatever it held -- a selection, not x * 0.  Forward and backward
+    use the same call."""
+    if x.dim() < 1 or x.numel() == 0 or not x.is_contiguous():
+        raise ValueError("drop_path: a contiguous tensor [B][...] expected")
+    if not 0.0 < pkeep <= 1.0:
+        raise ValueError("drop_path: pkeep must be in (0, 1]")
+    B = x.shape[0]
+    n = x.numel() // B
+    if not _native_t(x):
+        keep = drop_path_keep_ref(B, effective_seed(seed, counter), pkeep, x.device)
+        scale = torch.ones((), dtype=torch.float32, device=x.device) / torch.tensor(pkeep, dtype=torch.float32,
+                                                                                  device=x.device)
+        v = (x.reshape(B, n).float() * scale).to(x.dtype)
+        x.copy_(torch.where(keep.view(B, 1), v, torch.zeros_like(v)).view(x.shape))
+        return
+    _flat_bf16(x, who="drop_path")
+    native.check(_k().cxn_drop_path(x.data_ptr(), B, n, seed & 0xFFFFFFFF, _ctr(counter), float(pkeep), _stream()),
+                 "drop_path")
 
 
 # ----------------------------------------------------------------------------- prelu
