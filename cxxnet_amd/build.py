@@ -78,6 +78,13 @@ def kernel_compile_cmd(kernel_dir):
             "-munsafe-fp-atomics", "-Wno-unused-result", "-I" + kernel_dir]
 
 
+# per-file additions to kernel_compile_cmd.  conv_wgrad_direct.hip: no packed fp32 VALU ops
+# (v_pk_add/mul/fma_f32); its partial-tile sums stay plain per-element fp32 adds
+FILE_FLAGS = {
+    "conv_wgrad_direct.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def build_kernels(verbose=False, force=False, jobs=8) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "kernels", "*.h"))
@@ -91,7 +98,7 @@ def build_kernels(verbose=False, force=False, jobs=8) -> str:
         o = os.path.join(objdir, os.path.basename(s) + ".o")
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
-            jobs_list.append(common + ["-c", s, "-o", o])
+            jobs_list.append(common + FILE_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o])
     if jobs_list:
         with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
             list(ex.map(lambda c: _run(c, verbose), jobs_list))

@@ -24,6 +24,11 @@
 //     WHOLE tile (4 x 2 x 9 f32x4 = 288 AGPRs) over every fourth K-step, so per K-step a wave
 //     reads 4 dy + 18 x fragments for 72 MFMAs (0.31 reads per MFMA) with constant addresses.
 //     The four partial tiles meet through LDS after the loop.
+//   * Wide form (WC = 2, input channels per group a multiple of 64): block tile 64 co x 64 ci,
+//     the waves laid out 2 ci halves x 2 K halves, one image per stage.  Each wave keeps the same
+//     64 co x 32 ci register tile and the same reads per MFMA, but a stage's dy image serves
+//     twice the MFMAs: 62 instead of 88 staged bytes per MFMA, 13 instead of 19 LDS-DMAs per
+//     wave per stage, and the combine after the loop is 2-way.  Pairs halve and splits double.
 //   * Split over images: (pairs x splits) ~ one block per CU, XCD-contiguous so the blocks that
 //     read the same images share an L2.  No atomics: each block stores its partial tile with
 //     plain coalesced 16-byte stores into a workspace, and conv_wgrad_direct_reduce sums the
@@ -37,26 +42,30 @@ namespace {
 constexpr int NAGPR_ACC = 56;  // f32x4 accumulators kept in AGPRs (224 of the 256)
 
 
-template <int H, int W, int KS, int IPS>
+template <int H, int W, int KS, int IPS, int WC = 1>
 struct Wd {
+  static_assert(WC == 1 || WC == 2, "wave layout");
+  static constexpr int WK = 4 / WC;                      // waves along K (WC along ci)
   static constexpr int P = (KS - 1) / 2;
   static constexpr int T = KS * KS;
   static constexpr int PW = W + P;                       // slot pitch
   static constexpr int VR = H + P;                       // virtual rows per image
   static constexpr int WALK = (IPS * VR - P) * PW;       // output slots that can hold pixels
-  static constexpr int NK = (WALK + 127) / 128 * 4;      // K-steps per stage, a multiple of 4
-  static constexpr int KW4 = NK / 4;                     // K-steps per wave per stage
+  static constexpr int NK = (WALK + 32 * WK - 1) / (32 * WK) * WK;  // K-steps per stage, a multiple of WK
+  static constexpr int KW4 = NK / WK;                    // K-steps per wave per stage
   static constexpr int NKS = NK * 32;                    // dy slots per stage
   static constexpr int NX = (NKS + (KS - 1) * (PW + 1) + 31) / 32;  // x slot groups of 32
   static constexpr int NXS = NX * 32;
   static constexpr int XLEAD = P * PW + P;               // x slot of linear position 0
-  static constexpr int CO_U = 4, CI_U = 2;               // 64 co x 32 ci per block
+  static constexpr int CO_U = 4, CI_U = 2;               // 64 co x 32 ci per wave
+  static constexpr int CI_B = CI_U * WC;                 // ci units of 16 per block
   static constexpr int DYB = CO_U * NKS * 32;            // dy bytes per buffer
-  static constexpr int XB = CI_U * NXS * 32;
+  static constexpr int XB = CI_B * NXS * 32;
   static constexpr int BUF = DYB + XB;
   static constexpr int NQD = CO_U * NK / 4;              // dy DMA instructions per wave
-  static constexpr int NQX = (CI_U * NX + 3) / 4;        // x DMA instructions per wave (last maybe idle)
+  static constexpr int NQX = (CI_B * NX + 3) / 4;        // x DMA instructions per wave (last maybe idle)
   static constexpr int NACC = CO_U * CI_U * T;           // f32x4 accumulators per wave
+  static constexpr int NACC_B = NACC * WC;               // ... per block tile ([ci half][NACC])
   static_assert(2 * BUF <= 160 * 1024, "LDS");  // (the epilogue's chunked combine checks its own fit)
 };
 
@@ -73,13 +82,21 @@ __device__ __forceinline__ int slot_pixel(int lin) {
   return (img * H + row) * W + col;
 }
 
+// V: schedule bits (1, 2, 64: see launch_wd), 128: the wide form (WC = 2), and compile-time
+// ablation bits used while tuning (256 / 512: skip the dy / x DMAs, 1024: skip the fragment
+// reads, 2048: skip the MFMAs, 4096: skip the combine and the stores; results are then
+// meaningless -- 0 in every shipped launch, reached only through the probe bits of `splits`).
+constexpr int WD_WIDE = 128, WD_NO_DY = 256, WD_NO_X = 512, WD_NO_READ = 1024, WD_NO_MFMA = 2048, WD_NO_EPI = 4096;
+
 template <int H, int W, int KS, int IPS, int V>
 __global__ void __launch_bounds__(256, 1)
 conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, float *__restrict__ ws, int N, int C,
-                  int ldy, int Cg, int Cog, int npairs, int nci_b, int nco_b, int per, int nstages, int want_db) {
-  using G = Wd<H, W, KS, IPS>;
+                  int ldy, int Cg, int Cog, int npairs, int nci_b, int nco_b, int nsplit, int nstages, int want_db) {
+  constexpr int WC = (V & WD_WIDE) ? 2 : 1;
+  using G = Wd<H, W, KS, IPS, WC>;
   constexpr int T = G::T, NK = G::NK, KW4 = G::KW4, NKS = G::NKS, NX = G::NX, NXS = G::NXS, PW = G::PW;
   constexpr int CO_U = G::CO_U, CI_U = G::CI_U, BUF = G::BUF, DYB = G::DYB, NQD = G::NQD, NQX = G::NQX;
+  constexpr int WK = G::WK, CI_B = G::CI_B;
   constexpr int HW = H * W;
   __shared__ __attribute__((aligned(1024))) char smem[2 * BUF];
 
@@ -89,11 +106,14 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
   const int per_g = nco_b * nci_b;
   const int g = pair / per_g, rem = pair - g * per_g;
   const int cob = rem / nci_b, cib = rem - cob * nci_b;
-  const int ci0 = g * Cg + cib * 16 * CI_U, co0 = g * Cog + cob * 16 * CO_U;
-  const int sb = split * per, se = min(nstages, sb + per);
+  const int ci0 = g * Cg + cib * 16 * CI_B, co0 = g * Cog + cob * 16 * CO_U;
+  // balanced stage ranges: split k walks [k nstages / S, (k + 1) nstages / S)
+  const int sb = static_cast<int>(static_cast<long>(split) * nstages / nsplit);
+  const int se = static_cast<int>(static_cast<long>(split + 1) * nstages / nsplit);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wc = wave % WC, kp = wave / WC;  // this wave's ci half and K part (MFMA side only)
 
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_void *)smem)));
   // ---- per-lane DMA source offsets within a stage (fixed for the whole kernel)
@@ -110,7 +130,7 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
     const int q = wave + 4 * i;
     const int u = q / NX, sg = q - u * NX;
     const int pix = slot_pixel<H, W, KS, IPS>(32 * sg + (lane >> 1) - G::XLEAD);
-    vx[i] = (q < CI_U * NX && pix >= 0) ? static_cast<uint32_t>((pix * C + 16 * u + 8 * (lane & 1)) * 2) : OOB;
+    vx[i] = (q < CI_B * NX && pix >= 0) ? static_cast<uint32_t>((pix * C + 16 * u + 8 * (lane & 1)) * 2) : OOB;
   }
   // stage st -> buffer b: the DMAs of this wave (descriptors cover the stage's whole images; a
   // missing last image is out of range, so its slots read as zeros).  DMA i < NQD is dy
@@ -128,10 +148,10 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
     constexpr int i = decltype(ic)::value;
     const uint32_t base = lds0 + b * BUF + wave * 1024;  // wave-uniform LDS byte address
     if constexpr (i < NQD) {
-      dma16(rd, base + i * 4096, vd[i]);
-    } else {
+      if constexpr (!(V & WD_NO_DY)) dma16(rd, base + i * 4096, vd[i]);
+    } else if constexpr (!(V & WD_NO_X)) {
       constexpr int k = i - NQD;
-      if (wave + 4 * k < CI_U * NX) dma16(rx, base + DYB + k * 4096, vx[k]);
+      if (wave + 4 * k < CI_B * NX) dma16(rx, base + DYB + k * 4096, vx[k]);
     }
   };
   auto issue = [&](int st, int b) __attribute__((always_inline)) {
@@ -145,11 +165,11 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
   for (int hl = 0; hl < 2; ++hl) {
     const int sl = ((g4 >> 1) << 4) | (hl << 3) | ((g4 & 1) << 2) | (l16 >> 2);
-    const int o = (sl + 32 * wave) * 32 + 8 * (l16 & 3);  // this wave's first K-step
+    const int o = (sl + 32 * kp) * 32 + 8 * (l16 & 3);  // this wave's first K-step
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       bd[b][hl] = b * BUF + o;
-      bx[b][hl] = b * BUF + DYB + o;
+      bx[b][hl] = b * BUF + DYB + wc * CI_U * NXS * 32 + o;  // this wave's ci half
     }
   }
 
@@ -158,31 +178,40 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
   for (int i = 0; i < G::NACC; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 fa[2][CO_U], fb[3][CI_U];
+  if constexpr (V & WD_NO_READ) {
+#pragma unroll
+    for (int i = 0; i < 2 * CO_U; ++i) fa[i / CO_U][i % CO_U] = bf16x8{};
+#pragma unroll
+    for (int i = 0; i < 3 * CI_U; ++i) fb[i / CI_U][i % CI_U] = bf16x8{};
+  }
   // bias gradient (want_db): db[co] = sum over pixels of dy, as MFMAs of the dy fragments with a
-  // ones operand.  K-step k (= wave + 4 j of every stage) of co block cob is summed by the block
-  // with ci block k % nci_b, so each pixel counts once and the extra MFMAs (4 per summed K-step)
-  // are spread over the ci blocks (< 1 % of the MFMAs).
+  // ones operand.  K-step k (= kp + WK j of every stage) of co block cob is summed by the block
+  // with ci block k % nci_b (its waves of ci half 0: both halves read the same dy), so each pixel
+  // counts once and the extra MFMAs (4 per summed K-step) are spread over the ci blocks (< 1 %
+  // of the MFMAs).
   f32x4 accb[CO_U];
 #pragma unroll
   for (int m = 0; m < CO_U; ++m) accb[m] = f32x4{0.f, 0.f, 0.f, 0.f};
   bool dbj[KW4];
 #pragma unroll
-  for (int j = 0; j < KW4; ++j) dbj[j] = want_db && (wave + 4 * j) % nci_b == cib;
+  for (int j = 0; j < KW4; ++j) dbj[j] = want_db && wc == 0 && (kp + WK * j) % nci_b == cib;
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   bf16x8 ones = __builtin_bit_cast(bf16x8, s16x8{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80});
   asm volatile("" : "+v"(ones));  // opaque: not re-materialised next to its MFMAs
 
-  // K-step j (0..KW4-1) of this wave in buffer b: slots 32 (wave + 4 j) ..
+  // K-step j (0..KW4-1) of this wave in buffer b: slots 32 (kp + WK j) ..
   auto read_a = [&](int set, int b, int j) __attribute__((always_inline)) {
+    if constexpr (V & WD_NO_READ) return;
 #pragma unroll
     for (int m = 0; m < CO_U; ++m) {
-      const int off = (m * NKS + 128 * j) * 32;
+      const int off = (m * NKS + 32 * WK * j) * 32;
       fa[set][m] = frag_tr(smem + bd[b][0] + off, smem + bd[b][1] + off);
     }
   };
   auto read_bu = [&](int set, int b, int j, int t, int u) __attribute__((always_inline)) {
+    if constexpr (V & WD_NO_READ) return;
     const int kh = t / KS, kw = t - kh * KS;
-    const int off = (u * NXS + 128 * j + kh * PW + kw) * 32;
+    const int off = (u * NXS + 32 * WK * j + kh * PW + kw) * 32;
     fb[set][u] = frag_tr(smem + bx[b][0] + off, smem + bx[b][1] + off);
   };
   auto read_b = [&](int set, int b, int j, int t) __attribute__((always_inline)) {
@@ -235,7 +264,7 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
           constexpr int q = decltype(uc)::value;
           constexpr int m = q / CI_U, u = q % CI_U;
           constexpr int ai = (m * CI_U + u) * T + t;
-          mfma16<(ai < NAGPR_ACC)>(acc[ai], fa[ja][m], fb[sb3][u]);
+          if constexpr (!(V & WD_NO_MFMA)) mfma16<(ai < NAGPR_ACC)>(acc[ai], fa[ja][m], fb[sb3][u]);
           if constexpr ((V & 1) && j == 0 && q == 4) {
             static_for<NDMA>([&](auto ic) {
               constexpr int i = decltype(ic)::value;
@@ -260,7 +289,7 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
             if (more) read_a(ja ^ 1, B, j + 1);
           }
           if constexpr (q == CO_U * CI_U - 1 && t == T - 1) {
-            if (dbj[j]) {
+            if (!(V & WD_NO_MFMA) && dbj[j]) {
 #pragma unroll
               for (int mm = 0; mm < CO_U; ++mm) mfma_db(accb[mm], fa[ja][mm], ones);
             }
@@ -294,14 +323,16 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
 #pragma unroll
   for (int m = 0; m < CO_U; ++m) pin<false>(accb[m]);
 
-  // ---- the four waves' partial tiles meet through LDS (both stage buffers are free: the last
-  // stage ended with a barrier), CH accumulators at a time so that no more than a few sums are
-  // live in VGPRs: every wave writes its CH accumulators (lane l's f32x4 of accumulator i at
-  // byte (i - c0) * 1024 + 16 l of the wave's region), then wave w sums accumulators
-  // c0 + CH/4 w .. over the four regions and stores them (coalesced 1-KiB rows).
-  constexpr int NACC = G::NACC, CH = 24, NCH = NACC / CH, Q = CH / 4, RB = CH * 1024;
-  static_assert(NACC % CH == 0 && 4 * RB <= 2 * BUF, "epilogue chunks");
-  float *out = ws + (static_cast<long>(split) * npairs + pair) * (NACC * 256) + 4 * lane;
+  // ---- the WK waves of a ci half meet their partial tiles through LDS (both stage buffers are
+  // free: the last stage ended with a barrier), CH accumulators at a time so that no more than a
+  // few sums are live in VGPRs: every wave writes its CH accumulators (lane l's f32x4 of
+  // accumulator i at byte (i - c0) * 1024 + 16 l of the wave's region), then the wave of K part
+  // kp sums accumulators c0 + CH/WK kp .. over the WK regions of its ci half, in K-part order,
+  // and stores them (coalesced 1-KiB rows).  Block tile in the workspace: [ci half][NACC].
+  if constexpr (V & WD_NO_EPI) return;
+  constexpr int NACC = G::NACC, NACC_B = G::NACC_B, CH = 24, NCH = NACC / CH, Q = CH / WK, RB = CH * 1024;
+  static_assert(NACC % CH == 0 && CH % WK == 0 && 4 * RB <= 2 * BUF, "epilogue chunks");
+  float *out = ws + (static_cast<long>(split) * npairs + pair) * (NACC_B * 256) + wc * (NACC * 256) + 4 * lane;
   static_for<NCH>([&](auto cc) {
     constexpr int c0 = decltype(cc)::value * CH;
     static_for<CH>([&](auto ic) {
@@ -311,17 +342,18 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
     block_barrier();
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
-      const int i = Q * wave + k;
-      f32x4 v = *reinterpret_cast<const f32x4 *>(smem + i * 1024 + 16 * lane);
+      const int i = Q * kp + k;
+      f32x4 v = *reinterpret_cast<const f32x4 *>(smem + wc * RB + i * 1024 + 16 * lane);
 #pragma unroll
-      for (int w = 1; w < 4; ++w) v += *reinterpret_cast<const f32x4 *>(smem + w * RB + i * 1024 + 16 * lane);
+      for (int w = 1; w < WK; ++w) v += *reinterpret_cast<const f32x4 *>(smem + (w * WC + wc) * RB + i * 1024 + 16 * lane);
       *reinterpret_cast<f32x4 *>(out + (c0 + i) * 256) = v;
     }
     block_barrier();
   });
   if (want_db) {
     // every column of the ones-product holds the row sum: lanes of column 0 hand over their 16
-    // channels (16 m + 4 g4 + j) per wave, wave 0 sums the four waves and stores 64 partials
+    // channels (16 m + 4 g4 + j) per wave, wave 0 sums the four waves (zeros from the waves of
+    // ci half 1) and stores 64 partials
     float *sdb = reinterpret_cast<float *>(smem);
     if (l16 == 0) {
 #pragma unroll
@@ -332,19 +364,21 @@ conv_wgrad_direct(const bf16_t *__restrict__ x, const bf16_t *__restrict__ dy, f
     block_barrier();
     if (wave == 0) {
       const float v = sdb[lane] + sdb[64 + lane] + sdb[128 + lane] + sdb[192 + lane];
-      ws[static_cast<long>(gridDim.x) * (NACC * 256) + (static_cast<long>(split) * npairs + pair) * 64 + lane] = v;
+      ws[static_cast<long>(gridDim.x) * (NACC_B * 256) + (static_cast<long>(split) * npairs + pair) * 64 + lane] = v;
     }
   }
 }
 
 // dW[co][t][ci] += sum over splits of the partial tiles (fixed order).  Thread = (pair, acc i,
 // lane): its f32x4 holds output channels co0 + 16 m + 4 (lane >> 4) + j, input channel ci0 + 16 u +
-// (lane & 15), tap t, with i = (m CI_U + u) T + t.
+// (lane & 15), tap t, with i = (m CI_U + u) T + t; a block tile holds wcn (1, wide form 2) such
+// ci halves of 32 channels.
 template <int T>
 __global__ void __launch_bounds__(256)
 conv_wgrad_direct_reduce(const float *__restrict__ ws, float *__restrict__ dw, float *__restrict__ db, int nsplit,
-                         int npairs, int nci_b, int nco_b, int Cg, int Cog, float alpha) {
-  constexpr int CO_U = 4, CI_U = 2, NACC = CO_U * CI_U * T;
+                         int npairs, int nci_b, int nco_b, int Cg, int Cog, float alpha, int wcn) {
+  constexpr int CO_U = 4, CI_U = 2, NACC1 = CO_U * CI_U * T;
+  const int NACC = NACC1 * wcn;
   // the bias-gradient blocks come first (they start with the grid instead of trailing it)
   const int nbb = db != nullptr ? (npairs / nci_b + 3) / 4 : 0;
   if (static_cast<int>(blockIdx.x) < nbb) {
@@ -382,9 +416,10 @@ conv_wgrad_direct_reduce(const float *__restrict__ ws, float *__restrict__ dw, f
   const int per_g = nco_b * nci_b;
   const int g = pair / per_g, rem = pair - g * per_g;
   const int cob = rem / nci_b, cib = rem - cob * nci_b;
-  const int t = i % T, mu = i / T;
+  const int h = i / NACC1, i1 = i - h * NACC1;
+  const int t = i1 % T, mu = i1 / T;
   const int m = mu / CI_U, u = mu - m * CI_U;
-  const int ci = cib * 16 * CI_U + 16 * u + (lane & 15);
+  const int ci = (cib * wcn + h) * 16 * CI_U + 16 * u + (lane & 15);
   const int co = g * Cog + cob * 16 * CO_U + 16 * m + 4 * (lane >> 4);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -393,41 +428,40 @@ conv_wgrad_direct_reduce(const float *__restrict__ ws, float *__restrict__ dw, f
   }
 }
 
-template <int H, int W, int KS, int IPS>
-int launch_wd(const bf16_t *x, const bf16_t *dy, float *dw, float *db, float *ws, long ws_floats, int N, int C, int ldy,
-              int Cg, int Cog, int groups, int splits, float alpha, hipStream_t s) {
-  using G = Wd<H, W, KS, IPS>;
-  const int nci_b = Cg / 32, nco_b = Cog / 64;
-  const int npairs = groups * nci_b * nco_b;
-  const int nstages = (N + IPS - 1) / IPS;
-  int S = splits > 0 ? splits : 256 / npairs;
-  S = S < 1 ? 1 : (S > nstages ? nstages : S);
-  const int per = (nstages + S - 1) / S;
-  S = (nstages + per - 1) / per;  // every split holds at least one stage
-  const long need = static_cast<long>(S) * npairs * (G::NACC * 256 + 64);
-  if (ws_floats < need) return -4;
-  // schedule 65 (bits: 1 = the next stage's DMAs ride on K-step 0's taps, 64 = the two x
-  // fragments of tap t + 2 issued after MFMAs 1 and 3 of tap t); measured against the plain
-  // schedule (DMAs at the stage start, 101.6 -> ~100 / 112 -> 101 us on conv3, r5_wgrad_direct_*)
-  CXN_LAUNCH((conv_wgrad_direct<H, W, KS, IPS, 65>), dim3(static_cast<unsigned>(npairs * S)), dim3(256), 0, s, x, dy,
-             ws, N, C, ldy, Cg, Cog, npairs, nci_b, nco_b, per, nstages, db != nullptr ? 1 : 0);
-  const long blocks = (static_cast<long>(npairs) * G::NACC * 64 + 255) / 256 + (db != nullptr ? (npairs / nci_b + 3) / 4 : 0);
-  CXN_LAUNCH((conv_wgrad_direct_reduce<G::T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, ws, dw, db, S,
-             npairs, nci_b, nco_b, Cg, Cog, alpha);
-  return 0;
+// splits S of a launch: the request, or as many as keep pairs x S within the 256 CUs; every
+// split holds at least one stage (split k walks stages [k nstages / S, (k + 1) nstages / S))
+inline int wd_splits(int nstages, int npairs, int splits) {
+  const int S = splits > 0 ? splits : 256 / npairs;
+  return S < 1 ? 1 : (S > nstages ? nstages : S);
 }
 
-// workspace floats for a launch (0 when the shape is not served)
-template <int H, int W, int KS, int IPS>
+// workspace floats for a launch
+template <int H, int W, int KS, int IPS, int V>
 long ws_wd(int N, int Cg, int Cog, int groups, int splits) {
-  using G = Wd<H, W, KS, IPS>;
-  const int npairs = groups * (Cg / 32) * (Cog / 64);
+  using G = Wd<H, W, KS, IPS, (V & WD_WIDE) ? 2 : 1>;
+  const int npairs = groups * (Cg / (16 * G::CI_B)) * (Cog / 64);
+  return static_cast<long>(wd_splits((N + IPS - 1) / IPS, npairs, splits)) * npairs * (G::NACC_B * 256 + 64);
+}
+
+// schedule bits of V: 1 = the next stage's DMAs ride on K-step 0's taps, 64 = the two x
+// fragments of tap t + 2 issued after MFMAs 1 and 3 of tap t; 65 measured against the plain
+// schedule (DMAs at the stage start, 101.6 -> ~100 / 112 -> 101 us on conv3, r5_wgrad_direct_*)
+template <int H, int W, int KS, int IPS, int V>
+int launch_wd(const bf16_t *x, const bf16_t *dy, float *dw, float *db, float *ws, long ws_floats, int N, int C, int ldy,
+              int Cg, int Cog, int groups, int splits, float alpha, hipStream_t s) {
+  constexpr int WC = (V & WD_WIDE) ? 2 : 1;
+  using G = Wd<H, W, KS, IPS, WC>;
+  const int nci_b = Cg / (16 * G::CI_B), nco_b = Cog / 64;
+  const int npairs = groups * nci_b * nco_b;
   const int nstages = (N + IPS - 1) / IPS;
-  int S = splits > 0 ? splits : 256 / npairs;
-  S = S < 1 ? 1 : (S > nstages ? nstages : S);
-  const int per = (nstages + S - 1) / S;
-  S = (nstages + per - 1) / per;
-  return static_cast<long>(S) * npairs * (G::NACC * 256 + 64);
+  const int S = wd_splits(nstages, npairs, splits);
+  if (ws_floats < ws_wd<H, W, KS, IPS, V>(N, Cg, Cog, groups, splits)) return -4;
+  CXN_LAUNCH((conv_wgrad_direct<H, W, KS, IPS, V>), dim3(static_cast<unsigned>(npairs * S)), dim3(256), 0, s, x, dy,
+             ws, N, C, ldy, Cg, Cog, npairs, nci_b, nco_b, S, nstages, db != nullptr ? 1 : 0);
+  const long blocks = (static_cast<long>(npairs) * G::NACC_B * 64 + 255) / 256 + (db != nullptr ? (npairs / nci_b + 3) / 4 : 0);
+  CXN_LAUNCH((conv_wgrad_direct_reduce<G::T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, ws, dw, db, S,
+             npairs, nci_b, nco_b, Cg, Cog, alpha, WC);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -712,7 +746,8 @@ int launch_wt(const bf16_t *x, const bf16_t *dy, float *dw, float *ws, long ws_f
 // ldy) multiples of 8.  ws == nullptr: returns the workspace size in floats (0: not served).
 // Otherwise launches the kernel and the split reduction into dw (fp32 [Cout][K][K][Cg], +=
 // alpha * gradient) and, when db is given, the bias gradient (fp32 [Cout], += alpha * sum of dy
-// over pixels); -1 when not served, -4 when ws is too small.
+// over pixels); -1 when not served, -4 when ws is too small.  splits: 0 = as many as fill the
+// CUs, else the count (clamped to the stages).
 CXN_API long cxn_conv_wgrad_direct(const void *x, const void *dy, float *dw, float *db, float *ws, long ws_floats,
                                    int N, int H,
                                    int W, int C, int ldy, int Cg, int Cog, int groups, int KH, int KW, int pad_h,
@@ -723,6 +758,10 @@ CXN_API long cxn_conv_wgrad_direct(const void *x, const void *dy, float *dw, flo
   if (static_cast<long>(N) * H * W * (C > ldy ? C : ldy) >= (1L << 30)) return ws ? -1 : 0;
   hipStream_t s = S_;
   const bf16_t *xb = static_cast<const bf16_t *>(x), *dyb = static_cast<const bf16_t *>(dy);
+  // probe bits above the split count (benchmarks/wgrad_direct_probe.py; 0 in every real call):
+  // bits 16-17 force the 13 x 13 form (1: 64 x 32 tiles, 2: wide), bits 20-24 pick an ablation
+  const int probe = (splits >> 16) & 3, ablate = (splits >> 20) & 31;
+  splits &= 0xffff;
   if (KH == 5 && H == 27 && W == 27 && db == nullptr && Cg % 16 == 0 && Cog % 64 == 0) {  // tap-split form (conv2)
     // eight waves (2 per SIMD, K-steps alternating) over four: 119 vs 141 us at AlexNet b256
     if (!ws) return ws_wt<27, 27, 5, 14, 4, 8>(N, Cg, Cog, groups, splits);
@@ -731,14 +770,33 @@ CXN_API long cxn_conv_wgrad_direct(const void *x, const void *dy, float *dw, flo
     RET;
   }
   if (KH == 3 && H == 13 && W == 13) {
-    if (!ws) return ws_wd<13, 13, 3, 2>(N, Cg, Cog, groups, splits);
-    const int rc = launch_wd<13, 13, 3, 2>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
+    // wide form wherever the channels allow it (profiles/r8_wgrad_direct_probe.jsonl)
+    const bool wide = probe == 2 || (probe != 1 && Cg % 64 == 0);
+    if (wide && Cg % 64) return ws ? -1 : 0;
+    if (!ws) return wide ? ws_wd<13, 13, 3, 1, 65 | WD_WIDE>(N, Cg, Cog, groups, splits) : ws_wd<13, 13, 3, 2, 65>(N, Cg, Cog, groups, splits);
+    int rc = -1;
+#define WD13(ABL)                                                                                                       \
+  rc = wide ? launch_wd<13, 13, 3, 1, 65 | WD_WIDE | (ABL)>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, \
+                                                            splits, alpha, s)                                           \
+            : launch_wd<13, 13, 3, 2, 65 | (ABL)>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits,    \
+                                                  alpha, s)
+    switch (ablate) {
+      case 0: WD13(0); break;
+      case 1: WD13(WD_NO_DY); break;
+      case 2: WD13(WD_NO_X); break;
+      case 3: WD13(WD_NO_DY | WD_NO_X); break;
+      case 4: WD13(WD_NO_READ); break;
+      case 8: WD13(WD_NO_MFMA); break;
+      case 16: WD13(WD_NO_EPI); break;
+      default: return -1;
+    }
+#undef WD13
     if (rc != 0) return rc;
     RET;
   }
   if (KH == 3 && H == 14 && W == 14) {  // (VGG-16 conv5_x, GoogLeNet 4c / 4e): one image per stage
-    if (!ws) return ws_wd<14, 14, 3, 1>(N, Cg, Cog, groups, splits);
-    const int rc = launch_wd<14, 14, 3, 1>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
+    if (!ws) return ws_wd<14, 14, 3, 1, 65>(N, Cg, Cog, groups, splits);
+    const int rc = launch_wd<14, 14, 3, 1, 65>(xb, dyb, dw, db, ws, ws_floats, N, C, ldy, Cg, Cog, groups, splits, alpha, s);
     if (rc != 0) return rc;
     RET;
   }
