@@ -82,6 +82,7 @@ def kernel_compile_cmd(kernel_dir):
 # (v_pk_add/mul/fma_f32); its partial-tile sums stay plain per-element fp32 adds
 FILE_FLAGS = {
     "conv_wgrad_direct.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "gconv_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

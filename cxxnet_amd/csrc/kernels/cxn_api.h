@@ -259,6 +259,17 @@ CXN_API int cxn_dwconv_bwd_weight(const void *x, long xs, const void *dy, long d
                                   long ws_floats, int N, int H, int W, int C, int Cout, int groups, int KH, int KW,
                                   int stride, int pad_y, int pad_x, void *stream);
 
+// gconv_kernels.hip
+CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
+                          int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,
+                          int relu, void *stream);
+CXN_API int cxn_gconv_bwd_data(const void *dy, long dys, const void *w, void *dx, long dxs, int N, int H, int W,
+                               int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,
+                               int mask_relu, void *stream);
+CXN_API int cxn_gconv_bwd_weight(const void *x, long xs, const void *dy, long dys, float *dw, float *ws, long ws_floats,
+                                 int N, int H, int W, int C, int Cout, int groups, int KH, int KW, int stride,
+                                 int pad_y, int pad_x, void *stream);
+
 // optim_kernels.hip
 CXN_API int cxn_fused_update(const long *offs, const long *ns, const float *hyper, int nseg, float *w, float *g,
                              float *st1, float *st2, void *wb, int algo, float d1, float d2, void *stream);

@@ -774,6 +774,89 @@ def dwconv_backward_weight(x, dy, dw, g: ConvGeom, db=None):
                                                     ws.numel(), *_dw_args(g), _stream()), g, "dwconv_bwd_weight")
 
 
+# ---------------------------------------------------------------------------------- narrow groups
+# 3 x 3 convolution with many narrow groups (ResNeXt's 32 groups of 4 .. 32 channels) on the
+# block-diagonal MFMA kernels of csrc/kernels/gconv_kernels.hip: several groups share one MFMA, the
+# input halo of a pixel patch crosses L2 -> LDS once, the block-diagonal weight operand is built in
+# LDS from w itself.  The kernels bypass the tile table.  CXXNET_GC=0 switches the path off (such a
+# layer then takes the per-group GEMM route, which has no data gradient at 4 channels per group).
+_GC = os.environ.get("CXXNET_GC", "1") != "0"
+GC_SERVED = ("groups >= 4, C == Cout, C % 16 == 0, C / groups in {4, 8, 16}, KH == KW == 3, "
+             "pad_y == pad_x == 1, stride in {1, 2}")
+# The kernels also take 32 channels per group (gconv_forward and its siblings, called directly),
+# but conv layers are not routed there: at ResNeXt-50's two 32-wide sites (14 x 14 and 7 x 7 maps,
+# batch 64) the forward measured 49.7 us against 16.0 us and 19.2 against 13.7 for the per-group
+# GEMM (docs/performance.md), so that width keeps the GEMM route.
+GC_ROUTED_WIDTHS = (4, 8, 16)
+
+
+def is_narrow_group(g: ConvGeom) -> bool:
+    """Grouped, not depthwise, with whole groups of 4, 8, 16 or 32 channels on both sides.  A pure
+    function of the geometry."""
+    return (g.groups >= 4 and g.C == g.Cout and g.C % g.groups == 0 and g.C // g.groups in (4, 8, 16, 32))
+
+
+def gconv_served(g: ConvGeom) -> bool:
+    """The geometries conv layers run on cxn_gconv_*: the shape rule of serves() in
+    gconv_kernels.hip at the group widths where the kernels win (GC_ROUTED_WIDTHS), without launching."""
+    return (is_narrow_group(g) and g.C // g.groups in GC_ROUTED_WIDTHS and g.C % 16 == 0 and g.KH == 3 and g.KW == 3 and g.pad_y == 1 and g.pad_x == 1
+            and g.stride in (1, 2) and g.N >= 1 and g.H >= 1 and g.W >= 1)
+
+
+def _gc_units(C):
+    """Units of 16 channels per slice: 128 contiguous bytes per pixel where C allows."""
+    return 4 if C % 64 == 0 else (2 if C % 32 == 0 else 1)
+
+
+def gconv_wgrad_partials(g: ConvGeom):
+    """(P, workspace floats) of cxn_gconv_bwd_weight: the launcher's own formula.  An item is a
+    patch of R x 16 output pixels of one image (R = 8 at stride 1, 4 at stride 2); a block of
+    threads takes ipb consecutive items -- an even share of at most 512 // (channel slices) slabs
+    -- for one slice of 16 * units channels and writes its part of a slab of C 9 cg floats."""
+    R = 8 if g.stride == 1 else 4
+    items = g.N * _cdiv(g.Ho, R) * _cdiv(g.Wo, 16)
+    ny = g.C // (16 * _gc_units(g.C))
+    ipb = _cdiv(items, max(512 // ny, 1))
+    P = _cdiv(items, ipb)
+    return P, P * g.C * 9 * (g.C // g.groups)
+
+
+def _gc_route(g: ConvGeom, *acts) -> bool:
+    """The narrow-group kernels take this call: the geometry is served and every activation
+    operand is made of 16-byte aligned 8-channel vectors."""
+    return (_GC and gconv_served(g)
+            and all(t.stride(-1) == 1 and _pix(t) % 8 == 0 and t.data_ptr() % 16 == 0 for t in acts))
+
+
+def _gc_done(rc, g: ConvGeom, what: str):
+    if not served(rc, what):
+        raise ValueError(f"{what}: narrow-group geometry {g} declined by the kernel (served: {GC_SERVED})")
+
+
+def gconv_forward(x, w, bias, y, g: ConvGeom, relu=False):
+    """y = [relu](conv(x, w) + bias) on cxn_gconv_fwd."""
+    _gc_done(native.kernels().cxn_gconv_fwd(x.data_ptr(), _pix(x), w.data_ptr(),
+                                            bias.data_ptr() if bias is not None else None, y.data_ptr(), _pix(y),
+                                            *_dw_args(g), int(relu), _stream()), g, "gconv_fwd")
+
+
+def gconv_backward_data(dy, w, dx, g: ConvGeom, mask_relu=False):
+    """dx = conv_transpose(dy, w), every element of dx written (relu'-masked when mask_relu: dx
+    holds relu(z) on entry) on cxn_gconv_bwd_data, from w itself: no flipped copy."""
+    _gc_done(native.kernels().cxn_gconv_bwd_data(dy.data_ptr(), _pix(dy), w.data_ptr(), dx.data_ptr(), _pix(dx),
+                                                 *_dw_args(g), int(mask_relu), _stream()), g, "gconv_bwd_data")
+
+
+def gconv_backward_weight(x, dy, dw, g: ConvGeom):
+    """dw += the weight gradient on cxn_gconv_bwd_weight: fixed-order partial sums, bitwise
+    reproducible in every mode.  (No bias gradient: the caller sums dy itself.)"""
+    _, need = gconv_wgrad_partials(g)
+    ws = workspace("gconv_wgrad", need, dw.device, 1 << 16)
+    _gc_done(native.kernels().cxn_gconv_bwd_weight(x.data_ptr(), _pix(x), dy.data_ptr(), _pix(dy), dw.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), *_dw_args(g), _stream()),
+             g, "gconv_bwd_weight")
+
+
 def _fwd_operands(x, w, g: ConvGeom):
     """The forward implicit GEMM: A = the weights ([cg_out][kdim] per group), B = the im2col gather
     of x.  B's C is the input's pixel stride: a channel slice of a wider buffer (sibling outputs,
@@ -833,6 +916,8 @@ def conv_forward(x, w, bias, y, g: ConvGeom, relu=False):
         return
     if _DW and is_depthwise(g):
         return dwconv_forward(x, w, bias, y, g, relu=relu)
+    if _gc_route(g, x, y):
+        return gconv_forward(x, w, bias, y, g, relu=relu)
     cg = g.cg_in
     va = 8 if cg % 8 == 0 else 4
     if g.C == 4 and conv_rowrun_fwd2(x, w, bias, y, g, relu):  # padded 4-channel first layers (GoogLeNet conv1)
@@ -921,8 +1006,9 @@ def conv_forward_split(x, w, bias, y, y2, split, g: ConvGeom, relu=False):
 def conv_weight_flip_multi(items):
     """wt = w with (Cout, Cin) swapped and the taps reversed (the data-gradient GEMM's weight
     operand), for every (w, wt, geometry) of `items` in one launch."""
-    # (a depthwise data gradient reads w itself: nothing to flip)
-    items = [it for it in items if _native_t(it[0]) and not (_DW and is_depthwise(it[2]))]
+    # (a depthwise or narrow-group data gradient reads w itself: nothing to flip)
+    items = [it for it in items if _native_t(it[0]) and not (_DW and is_depthwise(it[2]))
+             and not (_GC and gconv_served(it[2]))]
     if not items:
         return
     n = len(items)
@@ -953,6 +1039,11 @@ def conv_backward_data(dy, w, dx, g: ConvGeom, wt_buf=None, mask_relu=False, wt_
     if _DW and is_depthwise(g):  # (no dbias epilogue: the caller sums it itself)
         dwconv_backward_data(dy, w, dx, g, mask_relu=mask_relu)
         return False
+    if _gc_route(g, dy, dx):  # (likewise)
+        gconv_backward_data(dy, w, dx, g, mask_relu=mask_relu)
+        return False
+    if _GC and gconv_served(g):  # (operands the kernels decline: conv_weight_flip_multi skipped this layer)
+        wt_ready = False
     cg_in = g.cg_in
     if g.cg_out % 8:
         raise ValueError("conv dgrad: output channels per group must be a multiple of 8 on the GPU path")
@@ -1001,6 +1092,8 @@ def conv_backward_data_add(dy, w, dx, add, g: ConvGeom, wt_buf, mask_relu=False,
     LDS-DMA tile of this signature ("cd" table entry); False (nothing done) otherwise, and the
     caller takes the separate data-gradient + sum path."""
     if not _native_t(dy) or g.stride != 1 or not _use("cd") or g.cg_out % 8 or _pix(add) != _pix(dx):
+        return False
+    if _GC and gconv_served(g):  # (no flipped weights are kept for a narrow-group layer)
         return False
     if tuple(add.shape) != tuple(dx.shape) or not _glds_cfg["on"]:
         return False
@@ -1148,6 +1241,9 @@ def conv_backward_weight(x, dy, dw, g: ConvGeom, db=None) -> bool:
     if _DW and is_depthwise(g):
         dwconv_backward_weight(x, dy, dw, g, db=db)
         return db is not None
+    if _gc_route(g, x, dy):  # (no bias-gradient epilogue: the caller sums dy itself)
+        gconv_backward_weight(x, dy, dw, g)
+        return False
     cg = g.cg_in
     va = 8 if cg % 8 == 0 else 4
     kd = g.kdim
