@@ -79,10 +79,15 @@ def kernel_compile_cmd(kernel_dir):
 
 
 # per-file additions to kernel_compile_cmd.  conv_wgrad_direct.hip: no packed fp32 VALU ops
-# (v_pk_add/mul/fma_f32); its partial-tile sums stay plain per-element fp32 adds
+# (v_pk_add/mul/fma_f32); its partial-tile sums stay plain per-element fp32 adds.  Every kernel
+# file added since is built the same way, whatever it computes: its fp32 arithmetic is then the
+# scalar instructions the source spells out, not pairs chosen by the compiler's packing pass
 FILE_FLAGS = {
     "conv_wgrad_direct.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gconv_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "dwconv_lk_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ln_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "gelu_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

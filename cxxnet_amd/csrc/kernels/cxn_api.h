@@ -259,6 +259,30 @@ CXN_API int cxn_dwconv_bwd_weight(const void *x, long xs, const void *dy, long d
                                   long ws_floats, int N, int H, int W, int C, int Cout, int groups, int KH, int KW,
                                   int stride, int pad_y, int pad_x, void *stream);
 
+// dwconv_lk_kernels.hip
+CXN_API int cxn_dwlk_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
+                         int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,
+                         int relu, void *stream);
+CXN_API int cxn_dwlk_bwd_data(const void *dy, long dys, const void *w, void *dx, long dxs, int N, int H, int W,
+                              int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,
+                              int mask_relu, void *stream);
+CXN_API int cxn_dwlk_bwd_weight(const void *x, long xs, const void *dy, long dys, float *dw, float *db, float *ws,
+                                long ws_floats, int N, int H, int W, int C, int Cout, int groups, int KH, int KW,
+                                int stride, int pad_y, int pad_x, void *stream);
+
+// ln_kernels.hip
+CXN_API long cxn_ln_rows_per_block(int C);
+CXN_API long cxn_ln_ws_floats(long rows, int C);
+CXN_API int cxn_ln_fwd(const void *x, void *y, const float *slope, const float *bias, float *mean, float *rstd,
+                       long rows, int C, float eps, void *stream);
+CXN_API int cxn_ln_bwd(const void *g, const void *x, void *dx, const float *slope, float *gslope, float *gbias,
+                       const float *mean, const float *rstd, float *ws, long ws_floats, long rows, int C,
+                       void *stream);
+
+// gelu_kernels.hip
+CXN_API int cxn_gelu_fwd(const void *x, void *y, long n, void *stream);
+CXN_API int cxn_gelu_bwd(const void *x, const void *g, void *dx, long n, void *stream);
+
 // gconv_kernels.hip
 CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
                           int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

@@ -352,31 +352,7 @@ __global__ __launch_bounds__(NT) void dwconv_wgrad_partial(const bf16_t *__restr
   }
 }
 
-// dw[e] += sum over the slabs; e past nw: db.  ML lanes per element each sum a run of consecutive
-// slabs in slab order, lane 0 then sums the lanes in lane order: a fixed order, and P / ML dependent
-// loads per lane instead of P (one lane per element ran the 3 x 3 x 32-channel layer's 512 slabs
-// in 60 us, most of the weight gradient's time)
-constexpr int ML = 16, MC = NT / ML;
-__global__ __launch_bounds__(NT) void dwconv_wgrad_merge(const float *__restrict__ ws, int P, long slab, float *dw,
-                                                         float *db, int nw, int C) {
-  __shared__ float s_sum[ML][MC];
-  const int el = threadIdx.x % MC, ln = threadIdx.x / MC;
-  const int e = blockIdx.x * MC + el;
-  const int ne = nw + (db ? C : 0);
-  const int chunk = (P + ML - 1) / ML;
-  const int p0 = ln * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
-  float sum = 0.f;
-  if (e < ne) {
-#pragma unroll 8
-    for (int p = p0; p < p1; ++p) sum += ws[static_cast<size_t>(p) * slab + e];
-  }
-  s_sum[ln][el] = sum;
-  __syncthreads();
-  if (ln != 0 || e >= ne) return;
-  for (int q = 1; q < ML; ++q) sum += s_sum[q][el];
-  if (e < nw) dw[e] += sum;
-  else db[e - nw] += sum;
-}
+#include "dw_wgrad_merge.h"  // dwconv_wgrad_merge: dw += the slabs in a fixed order (shared with dwconv_lk_kernels.hip)
 
 // what the kernels serve; Ho / Wo by the layer's rule
 static bool serves(int N, int H, int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

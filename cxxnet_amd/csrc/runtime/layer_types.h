@@ -49,6 +49,8 @@ enum : int {
   kGroupNorm = 46,
   kSilu = 47,
   kDropPath = 48,
+  kLayerNorm = 49,
+  kGelu = 50,
   kPairTestGap = 1024,
 };
 
@@ -70,6 +72,7 @@ inline int GetLayerType(const std::string &t) {
       {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
       {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
+      {"layer_norm", kLayerNorm}, {"gelu", kGelu},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -530,6 +530,35 @@ class SiluLayer(Layer):
             L.silu_backward(nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
 
 
+class GeluLayer(Layer):
+    """`gelu` (type id 50) -- an extension, no reference counterpart: the exact (erf) form
+    y = x Phi(x), Phi(x) = (1 + erf(x / sqrt 2)) / 2, the activation of ConvNeXt, 1 -> 1 on nodes of
+    any shape.  fp32 arithmetic, one rounding to the node's dtype; Phi is formed as
+    erfc(-x / sqrt 2) / 2, so both ends stay finite: y = -0 far left, y = x (the same bits) far
+    right.  Backward takes the derivative from the INPUT node (gelu is not monotonic): with g the
+    gradient held by the output node, dx = g (Phi(x) + x phi(x)) goes to x.gdst, which may be
+    x.data.  The output node must differ from the input node.  No parameters and no state."""
+    # the kernels are library launches with step-invariant arguments (HIP graphs replay them);
+    # the launch-list audit (tests/test_launch_hygiene_gpu.py's all-layer net) does not cover it
+    replay_audited = False
+    type_name = "gelu"
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "GeluLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "GeluLayer: gelu reads its input again in backward, so the output node must differ from the input "
+               "(no self-loop)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "GeluLayer: padded-channel input is not supported")
+        nodes_out[0].set_shape(*nodes_in[0].shape)
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        L.gelu_forward(nodes_in[0].data, nodes_out[0].data)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        if prop_grad:
+            L.gelu_backward(nodes_in[0].data, nodes_out[0].data, nodes_in[0].gdst)
+
+
 class DropPathLayer(Layer):
     """`drop_path` (type id 48) -- an extension, no reference counterpart: stochastic depth per
     sample (Huang et al. 2016, as the EfficientNets use it), a self-loop on the residual branch in
@@ -663,6 +692,84 @@ class GroupNormLayer(Layer):
     def backprop(self, prop_grad, nodes_in, nodes_out):
         g = self._view(nodes_out[0].data)
         L.gn_backward(g, self._view(nodes_in[0].data), self._view(nodes_in[0].gdst), self.params[0].w,
+                      self.params[0].g, self.params[1].g, self._state(g), prop_grad)
+
+    def save_model(self, fo: BinWriter):
+        fo.write_tensor(self.params[0].w)
+        fo.write_tensor(self.params[1].w)
+
+    def load_model(self, fi: BinReader):
+        self.loaded = [fi.read_tensor(1), fi.read_tensor(1)]
+
+    def loaded_values(self):
+        return self.loaded
+
+
+class LayerNormLayer(Layer):
+    """`layer_norm` (type id 49) -- an extension, no reference counterpart: layer normalisation over
+    the channels of every position (LayerNorm(C), channels-last, as ConvNeXt uses it), 1 -> 1, the
+    output shaped like the input.  The node is read as [rows][C], rows = B HW of an NHWC map (a
+    matrix node has rows = B); per row, with mean and the biased var over its C values,
+    rstd = (var + eps)^-1/2 and y = (x - mean) rstd slope[c] + bias[c], fp32 arithmetic and one
+    rounding.  Not group_norm with gn_group = 1, which normalises over the whole sample.
+        eps         default 1e-6;   init_slope default 1;   init_bias default 0
+    Backward, with g the gradient held by the output node and xhat = (x - mean) rstd:
+    gbias[c] += sum g, gslope[c] += sum g xhat over the rows, and with prop_grad
+    dx = rstd (slope[c] g - s1 / C - xhat s2 / C) into x.gdst, s1 / s2 the row's sums of slope g and
+    slope g xhat.  x is read from the input node again, so the output node must differ from the
+    input; x.gdst may be x.data or the output node's buffer.  slope ("wmat") and bias ("bias") are
+    arena parameters; the checkpoint holds slope, bias."""
+    replay_audited = False  # (as group_norm)
+    type_name = "layer_norm"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.init_slope = 1.0
+        self.init_bias = 0.0
+        self.eps = 1e-6
+        self._st = None
+        self.loaded = None
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "init_slope":
+            self.init_slope = float(val)
+        elif name == "init_bias":
+            self.init_bias = float(val)
+        elif name == "eps":
+            self.eps = float(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "LayerNormLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "LayerNormLayer: layer_norm reads its input again in backward, so the output node must differ from "
+               "the input (no self-loop)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "LayerNormLayer: padded-channel input is not supported")
+        nodes_out[0].set_shape(*nodes_in[0].shape)
+        self.channel = _num_feat(nodes_in[0])
+        _check(self.channel <= (2048 if self.channel % 8 == 0 else 1024),
+               "LayerNormLayer: %d channels: the kernels hold a row in registers up to 2048 channels (1024 when "
+               "the count is no multiple of 8)" % self.channel)
+        b, c, h, w = nodes_in[0].shape
+        self.max_rows = b * (c * h * w // self.channel)
+        self.params = [ParamSpec("wmat", (self.channel,), _bias_init(self.init_slope)),
+                       ParamSpec("bias", (self.channel,), _bias_init(self.init_bias))]
+
+    def _view(self, t):
+        return t.view(-1, self.channel)
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.LNState(self.max_rows, self.channel, x.device)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = self._view(nodes_in[0].data)
+        L.ln_forward(x, self._view(nodes_out[0].data), self.params[0].w, self.params[1].w, self.eps, self._state(x))
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        g = self._view(nodes_out[0].data)
+        L.ln_backward(g, self._view(nodes_in[0].data), self._view(nodes_in[0].gdst), self.params[0].w,
                       self.params[0].g, self.params[1].g, self._state(g), prop_grad)
 
     def save_model(self, fo: BinWriter):
@@ -994,6 +1101,8 @@ def _register():
     register(46, GroupNormLayer)
     register(47, SiluLayer)
     register(48, DropPathLayer)
+    register(49, LayerNormLayer)
+    register(50, GeluLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -457,6 +457,10 @@ class ConvolutionLayer(Layer):
             ops.conv_forward(nodes_in[0].data, S["w_all"], S["b_all"], S["H"][:self.geo.N], self._sib_geo(S["ctot"]),
                              relu=self.fuse_relu)
             return
+        # large-kernel depthwise (7 x 7 .. 11 x 11: ConvNeXt) on the LDS stencils; no GEMM serves it
+        if ops.gemm.dwlk_route(self.geo, nodes_in[0].data, nodes_out[0].data):
+            ops.gemm.dwlk_forward(nodes_in[0].data, self.w.wb, bias, nodes_out[0].data, self.geo, relu=self.fuse_relu)
+            return
         # few-channel first layers on direct kernels that pad on the fly (GoogLeNet conv1: the
         # row-run forward; VGG conv1_1: conv_fewc); a zero-bordered copy is then built only by a
         # weight-gradient pass that needs it
@@ -498,6 +502,12 @@ class ConvolutionLayer(Layer):
                 ops.conv_backward_data(H, S["w_all"], S["dx_node"].gdst, gall, S["wt"], wt_ready=ready)
             return
         want_db = self.b is not None and not self.bias_done and self.ctx.is_gpu
+        if ops.gemm.dwlk_route(self.geo, x, dy, nodes_in[0].gdst):  # (as forward: weight, bias and data gradient)
+            ops.gemm.dwlk_backward_weight(x, dy, self.w.g, self.geo, db=self.b.g if want_db else None)
+            self.bias_done = False
+            if prop_grad:
+                ops.gemm.dwlk_backward_data(dy, self.w.wb, nodes_in[0].gdst, self.geo, mask_relu=self.grad_mask_relu)
+            return
         if self.geo.C <= 4 and self.ctx.is_gpu and ops.gemm.conv_wgrad_rowrun(x, dy, self.w.g, self.geo):
             db_done = False  # (few-channel first layer, padding staged on the fly: no bordered copy)
         else:

@@ -774,6 +774,76 @@ def dwconv_backward_weight(x, dy, dw, g: ConvGeom, db=None):
                                                     ws.numel(), *_dw_args(g), _stream()), g, "dwconv_bwd_weight")
 
 
+# ------------------------------------------------------------------------ large-kernel depthwise
+# 7 x 7 / 9 x 9 / 11 x 11 depthwise convolution (ConvNeXt's token mixer) on the LDS stencils of
+# csrc/kernels/dwconv_lk_kernels.hip.  conv_forward and its siblings keep raising for these
+# geometries (no GEMM serves a depthwise layer): ConvolutionLayer asks dwlk_route first.
+# CXXNET_DWLK=0 switches the path off.
+_DWLK = os.environ.get("CXXNET_DWLK", "1") != "0"
+DWLK_SERVED = ("groups == C == Cout, C % 8 == 0, KH == KW in {7, 9, 11}, stride 1, pad_y and pad_x in [0, K)")
+DWLK_PATCH = 16        # output pixels per block patch and axis ...
+DWLK_SMALL_MAP = 8     # ... 8 on maps of at most 8 x 8, which are one patch per image
+DWLK_GROUPS = (8, 16)  # 8-channel groups per block: (patch 16, patch 8)
+
+
+def dwlk_served(g: ConvGeom) -> bool:
+    """The shape rule of cxn_dwlk_* (serves() in dwconv_lk_kernels.hip), without launching.  A pure
+    function of the geometry."""
+    return (is_depthwise(g) and g.Cout == g.C and g.C % 8 == 0 and g.KH == g.KW and g.KH in (7, 9, 11)
+            and g.stride == 1 and 0 <= g.pad_y < g.KH and 0 <= g.pad_x < g.KW
+            and g.H + 2 * g.pad_y >= g.KH and g.W + 2 * g.pad_x >= g.KW)
+
+
+def dwlk_route(g: ConvGeom, *acts) -> bool:
+    """The large-kernel depthwise kernels take this call: switched on, the geometry served, every
+    activation operand native bf16 made of 16-byte aligned 8-channel vectors."""
+    return (_DWLK and dwlk_served(g)
+            and all(_native_t(t) and t.stride(-1) == 1 and _pix(t) % 8 == 0 and t.data_ptr() % 16 == 0 for t in acts))
+
+
+def dwlk_wgrad_partials(g: ConvGeom):
+    """(P, workspace floats) of cxn_dwlk_bwd_weight: the launcher's own formula.  An item is a
+    patch of 16 x 16 output pixels of one image (8 x 8 when the map is at most 8 x 8); a block takes
+    ipb consecutive items -- an even share of at most 512 // (channel blocks) slabs -- for one block
+    of 8 (16) channel groups and writes its part of a slab of C (K K + 1) floats (dw, then db)."""
+    small = g.Ho <= DWLK_SMALL_MAP and g.Wo <= DWLK_SMALL_MAP
+    pt = DWLK_SMALL_MAP if small else DWLK_PATCH
+    items = g.N * _cdiv(g.Ho, pt) * _cdiv(g.Wo, pt)
+    ny = _cdiv(g.C // 8, DWLK_GROUPS[1] if small else DWLK_GROUPS[0])
+    ipb = _cdiv(items, max(512 // ny, 1))
+    P = _cdiv(items, ipb)
+    return P, P * g.C * (g.KH * g.KW + 1)
+
+
+def _dwlk_done(rc, g: ConvGeom, what: str):
+    if not served(rc, what):
+        raise ValueError(f"{what}: depthwise geometry {g} declined by the kernel (served: {DWLK_SERVED})")
+
+
+def dwlk_forward(x, w, bias, y, g: ConvGeom, relu=False):
+    """y = [relu](dwconv(x, w) + bias) on cxn_dwlk_fwd; ValueError for a geometry not served."""
+    _dwlk_done(native.kernels().cxn_dwlk_fwd(x.data_ptr(), _pix(x), w.data_ptr(),
+                                             bias.data_ptr() if bias is not None else None, y.data_ptr(), _pix(y),
+                                             *_dw_args(g), int(relu), _stream()), g, "dwlk_fwd")
+
+
+def dwlk_backward_data(dy, w, dx, g: ConvGeom, mask_relu=False):
+    """dx = dwconv_transpose(dy, w), every element of dx written (relu'-masked when mask_relu: dx
+    holds relu(z) on entry) on cxn_dwlk_bwd_data, from w itself: no flipped copy."""
+    _dwlk_done(native.kernels().cxn_dwlk_bwd_data(dy.data_ptr(), _pix(dy), w.data_ptr(), dx.data_ptr(), _pix(dx),
+                                                  *_dw_args(g), int(mask_relu), _stream()), g, "dwlk_bwd_data")
+
+
+def dwlk_backward_weight(x, dy, dw, g: ConvGeom, db=None):
+    """dw += the depthwise weight gradient, db (optional) += the bias gradient in the same pass, on
+    cxn_dwlk_bwd_weight: fixed-order partial sums, bitwise reproducible."""
+    _, need = dwlk_wgrad_partials(g)
+    ws = workspace("dwlk_wgrad", need, dw.device, 1 << 16)
+    _dwlk_done(native.kernels().cxn_dwlk_bwd_weight(x.data_ptr(), _pix(x), dy.data_ptr(), _pix(dy), dw.data_ptr(),
+                                                    db.data_ptr() if db is not None else None, ws.data_ptr(),
+                                                    ws.numel(), *_dw_args(g), _stream()), g, "dwlk_bwd_weight")
+
+
 # ---------------------------------------------------------------------------------- narrow groups
 # 3 x 3 convolution with many narrow groups (ResNeXt's 32 groups of 4 .. 32 channels) on the
 # block-diagonal MFMA kernels of csrc/kernels/gconv_kernels.hip: several groups share one MFMA, the

@@ -284,6 +284,74 @@ def gn_backward(g, x, dx, slope, gslope, gbias, st: GNState, prop_grad: bool):
                  "gn_bwd")
 
 
+# ----------------------------------------------------------------------------- layer norm
+class LNState:
+    """Per-layer device buffers of layer_norm, sized once for the largest batch: mean and rstd
+    [rows] of the last forward and the slab workspace of the backward's fixed-order column sums
+    (csrc/kernels/ln_kernels.hip).  A smaller batch uses their leading rows."""
+
+    def __init__(self, max_rows, C, device):
+        self.mean = torch.zeros(max_rows, dtype=torch.float32, device=device)
+        self.rstd = torch.zeros(max_rows, dtype=torch.float32, device=device)
+        self.ws = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_ln_ws_floats(int(max_rows), int(C)))
+            self.ws = torch.zeros(max(n, 1), dtype=torch.float32, device=device)
+
+
+def ln_rows_per_block(C: int) -> int:
+    """Rows one block of the layer_norm kernels holds at C channels."""
+    return int(_k().cxn_ln_rows_per_block(int(C)))
+
+
+def ln_forward(x, y, slope, bias, eps, st: LNState):
+    """x, y [rows][C].  Per row: mean, biased var over C, rstd = (var + eps)^-1/2 into st.mean /
+    st.rstd, and y = (x - mean) rstd slope[c] + bias[c].  y must not alias x."""
+    rows, C = x.shape
+    if rows > st.mean.shape[0]:
+        raise ValueError("ln_forward: %d rows, state sized for %d" % (rows, st.mean.shape[0]))
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("ln_forward: y must not alias x (backward reads x again)")
+    if not _native_t(x):
+        v = x.float()
+        mean = v.mean(1, keepdim=True)
+        d = v - mean
+        rstd = 1.0 / torch.sqrt((d * d).mean(1, keepdim=True) + eps)
+        st.mean[:rows].copy_(mean.reshape(rows))
+        st.rstd[:rows].copy_(rstd.reshape(rows))
+        y.copy_(d * rstd * slope + bias)
+        return
+    _flat_bf16(x, y, who="ln_forward")
+    native.check(_k().cxn_ln_fwd(x.data_ptr(), y.data_ptr(), slope.data_ptr(), bias.data_ptr(), st.mean.data_ptr(),
+                                 st.rstd.data_ptr(), rows, C, float(eps), _stream()), "ln_fwd")
+
+
+def ln_backward(g, x, dx, slope, gslope, gbias, st: LNState, prop_grad: bool):
+    """With xhat = (x - mean) rstd of the last forward: gbias[c] += sum g, gslope[c] += sum g xhat
+    over the rows, and with prop_grad dx = rstd (slope[c] g - s1 / C - xhat s2 / C), s1 = sum
+    slope g and s2 = sum slope g xhat over the row.  dx may alias x or g; without prop_grad it is
+    not written."""
+    rows, C = g.shape
+    if not _native_t(g):
+        mean, rstd = st.mean[:rows].reshape(rows, 1), st.rstd[:rows].reshape(rows, 1)
+        g32 = g.float()
+        xh = (x.float() - mean) * rstd
+        gbias.add_(g32.sum(0))
+        gslope.add_((g32 * xh).sum(0))
+        if prop_grad:
+            sg = g32 * slope
+            s1 = sg.sum(1, keepdim=True)
+            s2 = (sg * xh).sum(1, keepdim=True)
+            dx.copy_(rstd * (sg - s1 / C - xh * s2 / C))
+        return
+    _flat_bf16(g, x, who="ln_backward")
+    if prop_grad:
+        _flat_bf16(dx, who="ln_backward")
+    native.check(_k().cxn_ln_bwd(g.data_ptr(), x.data_ptr(), dx.data_ptr() if prop_grad else None, slope.data_ptr(),
+                                 gslope.data_ptr(), gbias.data_ptr(), st.mean.data_ptr(), st.rstd.data_ptr(),
+                                 st.ws.data_ptr(), st.ws.numel(), rows, C, _stream()), "ln_bwd")
+
+
 # ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
 class AddState:
     """The relu mask of an `add` layer with add_relu = 1, sized once for the layer's largest
@@ -514,6 +582,43 @@ def silu_backward(x, g, dx):
         return
     _flat_bf16(x, g, dx, who="silu")
     native.check(_k().cxn_silu_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), _stream()), "silu_bwd")
+
+
+# ----------------------------------------------------------------------------- gelu
+def _cdf32(v):
+    """Phi(x) = erfc(-x / sqrt 2) / 2 in fp32, the kernels' formulation: no cancellation on the
+    left, +0 and 1 exactly at the ends"""
+    return 0.5 * torch.erfc(v * -0.7071067811865476)
+
+
+def gelu_forward(x, y):
+    """y = x Phi(x) (the exact, erf form) in fp32, one rounding to y's dtype.  y must not alias x."""
+    if x.numel() != y.numel():
+        raise ValueError("gelu: x and y of one size expected")
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("gelu: y must not alias x (backward reads x again)")
+    if not _native_t(x):
+        v = x.float()
+        y.copy_((v * _cdf32(v)).view(y.shape))
+        return
+    _flat_bf16(x, y, who="gelu")
+    native.check(_k().cxn_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "gelu_fwd")
+
+
+def gelu_backward(x, g, dx):
+    """dx = g (Phi(x) + x phi(x)), phi(x) = e^(-x x / 2) / sqrt(2 pi), the derivative taken from the
+    layer's INPUT x, in fp32, one rounding.  dx may alias x; it must not alias g."""
+    if not x.numel() == g.numel() == dx.numel():
+        raise ValueError("gelu: x, g and dx of one size expected")
+    if dx.data_ptr() == g.data_ptr():
+        raise ValueError("gelu: dx must not alias g (it may alias x)")
+    if not _native_t(g):
+        v, gv = x.float(), g.float().view(x.shape)
+        pdf = 0.3989422804014327 * torch.exp(-0.5 * (v * v))
+        dx.copy_((gv * (_cdf32(v) + v * pdf)).view(dx.shape))
+        return
+    _flat_bf16(x, g, dx, who="gelu")
+    native.check(_k().cxn_gelu_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), _stream()), "gelu_bwd")
 
 
 # ----------------------------------------------------------------------------- drop_path (per-sample dropout)
