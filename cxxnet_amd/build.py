@@ -88,6 +88,7 @@ FILE_FLAGS = {
     "dwconv_lk_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ln_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gelu_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "attn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

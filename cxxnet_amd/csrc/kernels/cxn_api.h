@@ -283,6 +283,13 @@ CXN_API int cxn_ln_bwd(const void *g, const void *x, void *dx, const float *slop
 CXN_API int cxn_gelu_fwd(const void *x, void *y, long n, void *stream);
 CXN_API int cxn_gelu_bwd(const void *x, const void *g, void *dx, long n, void *stream);
 
+// attn_kernels.hip
+CXN_API int cxn_attn_tile(int d, int *rows_per_block, int *keys_per_chunk);
+CXN_API int cxn_attn_fwd(const void *qkv, void *out, float *lse, float *lse2, int B, int T, int C, int nhead,
+                         void *stream);
+CXN_API int cxn_attn_bwd(const void *qkv, const void *dout, const float *lse2, float *dsum, void *dqkv,
+                         void *dq_stage, int B, int T, int C, int nhead, void *stream);
+
 // gconv_kernels.hip
 CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
                           int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

@@ -51,6 +51,7 @@ enum : int {
   kDropPath = 48,
   kLayerNorm = 49,
   kGelu = 50,
+  kAttention = 51,
   kPairTestGap = 1024,
 };
 
@@ -72,7 +73,7 @@ inline int GetLayerType(const std::string &t) {
       {"batch_norm_ma", kBatchNormMA}, {"add", kAdd}, {"ch_scale", kChScale},
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
       {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
-      {"layer_norm", kLayerNorm}, {"gelu", kGelu},
+      {"layer_norm", kLayerNorm}, {"gelu", kGelu}, {"attention", kAttention},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

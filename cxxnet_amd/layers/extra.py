@@ -1,6 +1,6 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
-ch_scale, relu6 / hsigmoid / hswish, group_norm, silu and drop_path.
+ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu and attention.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
@@ -783,6 +783,73 @@ class LayerNormLayer(Layer):
         return self.loaded
 
 
+class AttentionLayer(Layer):
+    """`attention` (type id 51) -- an extension, no reference counterpart: multi-head
+    self-attention over the positions of a map, 1 -> 1, no parameters (the qkv and output
+    projections are ordinary 1x1 convs).  The input node [B, 3 C, H, W] is read as rows [B T][3 C],
+    T = H W (a matrix node has T = 1); channel s C + h d + j is component j of head h of q (s = 0),
+    k (1), v (2), d = C / nhead -- what a fused qkv projection followed by
+    reshape(B, T, 3, nhead, d) yields.  The output node is [B, C, H, W].
+        nhead       required; d must be 32 or 64, and 1 <= T <= 1024
+    Forward, per sample and head: S = Q K^T / sqrt(d), P = softmax over the keys in fp32, O = P V,
+    one rounding at the store; no mask, no dropout on P.  The log-sum-exp of every row is kept
+    (ops.layer_ops.AttnState).  Backward, with g = dO held by the output node (O itself is gone):
+    dP = dO V^T, D_i = sum_j P_ij dP_ij, dV = P^T dO, dS = P (dP - D), dQ = dS K / sqrt(d),
+    dK = dS^T Q / sqrt(d), written as [B T][3 C] into x.gdst only with prop_grad.  qkv is read from
+    the input node again, so the output node must differ from the input; x.gdst may be x.data.
+    Nothing to save in a checkpoint."""
+    replay_audited = False  # (as layer_norm)
+    type_name = "attention"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.nhead = 0
+        self._st = None
+        self.bf16_products = False  # torch path: round P and dS as the HIP kernels do (a test's measuring switch)
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "nhead":
+            self.nhead = int(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, "AttentionLayer: only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               "AttentionLayer: attention reads its input again in backward, so the output node must differ from "
+               "the input (no self-loop)")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], "AttentionLayer: padded-channel input is not supported")
+        _check(self.nhead > 0, "AttentionLayer: must set nhead")
+        b, c, h, w = nodes_in[0].shape
+        c3 = _num_feat(nodes_in[0])
+        self.tokens = c * h * w // c3
+        _check(c3 % (3 * self.nhead) == 0,
+               "AttentionLayer: %d input channels are not 3 x nhead = %d x a head width" % (c3, self.nhead))
+        self.channel = c3 // 3
+        d = self.channel // self.nhead
+        _check(d in (32, 64), "AttentionLayer: head width %d: the kernels serve 32 and 64" % d)
+        _check(1 <= self.tokens <= 1024, "AttentionLayer: %d positions: the kernels serve 1 to 1024" % self.tokens)
+        if nodes_in[0].is_mat():
+            nodes_out[0].set_shape(b, 1, 1, self.channel)
+        else:
+            nodes_out[0].set_shape(b, self.channel, h, w)
+        self.max_batch = b
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.AttnState(self.max_batch, self.tokens, self.channel, self.nhead, x.device, x.dtype)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.attn_forward(x, nodes_out[0].data.view(-1, self.channel), x.shape[0] // self.tokens, self.nhead,
+                       self._state(x), self.bf16_products)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.attn_backward(nodes_out[0].data.view(-1, self.channel), x, nodes_in[0].gdst.view(-1, 3 * self.channel),
+                        x.shape[0] // self.tokens, self.nhead, self._state(x), prop_grad, self.bf16_products)
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -1103,6 +1170,7 @@ def _register():
     register(48, DropPathLayer)
     register(49, LayerNormLayer)
     register(50, GeluLayer)
+    register(51, AttentionLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

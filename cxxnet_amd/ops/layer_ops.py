@@ -1,5 +1,6 @@
 """Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
-extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path.
+extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path,
+layer_norm, gelu, attention.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -350,6 +351,94 @@ def ln_backward(g, x, dx, slope, gslope, gbias, st: LNState, prop_grad: bool):
     native.check(_k().cxn_ln_bwd(g.data_ptr(), x.data_ptr(), dx.data_ptr() if prop_grad else None, slope.data_ptr(),
                                  gslope.data_ptr(), gbias.data_ptr(), st.mean.data_ptr(), st.rstd.data_ptr(),
                                  st.ws.data_ptr(), st.ws.numel(), rows, C, _stream()), "ln_bwd")
+
+
+# ----------------------------------------------------------------------------- attention
+class AttnState:
+    """Per-layer device buffers of attention, sized once for the largest batch: the fp32
+    log-sum-exp of every softmax row and the backward's row term D, [B nhead T] each, and the
+    [B T][C] staging buffer dQ passes through when the gradient overwrites qkv in place
+    (csrc/kernels/attn_kernels.hip).  A smaller batch uses their leading part."""
+
+    def __init__(self, max_batch, T, C, nhead, device, dtype=torch.bfloat16):
+        self.lse = torch.zeros(max_batch * nhead * T, dtype=torch.float32, device=device)
+        self.lse2 = torch.zeros(max_batch * nhead * T, dtype=torch.float32, device=device)  # lse in log2 units (HIP path)
+        self.dsum = torch.zeros(max_batch * nhead * T, dtype=torch.float32, device=device)
+        self.dq = torch.zeros(max_batch * T, C, dtype=dtype, device=device) if dtype == torch.bfloat16 else None
+
+
+def attn_tile(d: int):
+    """(rows a block owns, keys per streamed chunk) of the attention kernels at head width d."""
+    import ctypes
+    r, k = ctypes.c_int(0), ctypes.c_int(0)
+    native.check(_k().cxn_attn_tile(int(d), ctypes.byref(r), ctypes.byref(k)), "attn_tile")
+    return r.value, k.value
+
+
+def _attn_heads(qkv, B, nhead):
+    """q, k, v as [B, nhead, T, d] fp32 views-turned-copies of qkv [B T][3 C]."""
+    rows, C3 = qkv.shape
+    T, C = rows // B, C3 // 3
+    v = qkv.float().view(B, T, 3, nhead, C // nhead).permute(2, 0, 3, 1, 4)
+    return v[0], v[1], v[2]
+
+
+def _bf16_round(t):
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def attn_forward(qkv, out, B, nhead, st: AttnState, bf16_products=False):
+    """qkv [B T][3 C] (channel s C + h d + j: component j of head h of q, k, v for s = 0, 1, 2),
+    out [B T][C].  Per sample and head O = softmax(Q K^T / sqrt(d)) V with the softmax in fp32;
+    st.lse receives every row's log-sum-exp.  out must not alias qkv.  bf16_products (torch path
+    only): round P to bf16 before P V as the HIP kernels do, to measure what that rounding adds."""
+    rows, C3 = qkv.shape
+    T, C = rows // B, C3 // 3
+    if B * nhead * T > st.lse.shape[0]:
+        raise ValueError("attn_forward: batch %d, state sized for %d rows" % (B, st.lse.shape[0]))
+    if qkv.data_ptr() == out.data_ptr():
+        raise ValueError("attn_forward: out must not alias qkv (backward reads qkv again)")
+    if not _native_t(qkv):
+        q, k, v = _attn_heads(qkv, B, nhead)
+        s = q @ k.transpose(-1, -2) / (C // nhead) ** 0.5
+        lse = torch.logsumexp(s, -1, keepdim=True)
+        st.lse[:B * nhead * T].copy_(lse.reshape(-1))
+        p = torch.exp(s - lse)
+        o = (_bf16_round(p) if bf16_products else p) @ v
+        out.copy_(o.permute(0, 2, 1, 3).reshape(rows, C))
+        return
+    _flat_bf16(qkv, out, who="attn_forward")
+    native.check(_k().cxn_attn_fwd(qkv.data_ptr(), out.data_ptr(), st.lse.data_ptr(), st.lse2.data_ptr(), B, T, C, nhead,
+                                   _stream()), "attn_fwd")
+
+
+def attn_backward(g, qkv, dqkv, B, nhead, st: AttnState, prop_grad: bool, bf16_products=False):
+    """g [B T][C] = dO.  With P = exp(S - lse) of the last forward, dP = dO V^T and
+    D_i = sum_j P_ij dP_ij (into st.dsum): dV = P^T dO, dS = P (dP - D), dQ = dS K / sqrt(d),
+    dK = dS^T Q / sqrt(d), written as [B T][3 C] into dqkv, which may be qkv.  Without prop_grad
+    nothing is computed or written.  bf16_products (torch path only): P and dS are rounded to bf16
+    before the three products that take them, as in the HIP kernels."""
+    if not prop_grad:
+        return
+    rows, C3 = qkv.shape
+    T, C = rows // B, C3 // 3
+    if not _native_t(g):
+        q, k, v = _attn_heads(qkv, B, nhead)
+        sc = 1.0 / (C // nhead) ** 0.5
+        do = g.float().view(B, T, nhead, C // nhead).permute(0, 2, 1, 3)
+        p = torch.exp(q @ k.transpose(-1, -2) * sc - st.lse[:B * nhead * T].view(B, nhead, T, 1))
+        dp = do @ v.transpose(-1, -2)
+        d = (p * dp).sum(-1, keepdim=True)
+        st.dsum[:B * nhead * T].copy_(d.reshape(-1))
+        ds = p * (dp - d)
+        if bf16_products:
+            p, ds = _bf16_round(p), _bf16_round(ds)
+        grads = torch.stack([ds @ k * sc, ds.transpose(-1, -2) @ q * sc, p.transpose(-1, -2) @ do])
+        dqkv.copy_(grads.permute(1, 3, 0, 2, 4).reshape(rows, C3))
+        return
+    _flat_bf16(g, qkv, dqkv, who="attn_backward")
+    native.check(_k().cxn_attn_bwd(qkv.data_ptr(), g.data_ptr(), st.lse2.data_ptr(), st.dsum.data_ptr(),
+                                   dqkv.data_ptr(), st.dq.data_ptr(), B, T, C, nhead, _stream()), "attn_bwd")
 
 
 # ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
