@@ -89,6 +89,7 @@ FILE_FLAGS = {
     "ln_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gelu_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "wattn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

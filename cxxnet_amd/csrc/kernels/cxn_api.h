@@ -290,6 +290,14 @@ CXN_API int cxn_attn_fwd(const void *qkv, void *out, float *lse, float *lse2, in
 CXN_API int cxn_attn_bwd(const void *qkv, const void *dout, const float *lse2, float *dsum, void *dqkv,
                          void *dq_stage, int B, int T, int C, int nhead, void *stream);
 
+// wattn_kernels.hip
+CXN_API long cxn_wattn_ws_floats(long B, int H, int W, int C, int nhead, int ws, int shift);
+CXN_API int cxn_wattn_fwd(const void *qkv, void *out, const float *bias, float *lse, float *lse2, long B, int H,
+                          int W, int C, int nhead, int ws, int shift, void *stream);
+CXN_API int cxn_wattn_bwd(const void *qkv, const void *dout, const float *bias, const float *lse2, void *dqkv,
+                          float *gbias, float *slabs, long ws_floats, long B, int H, int W, int C, int nhead, int ws,
+                          int shift, void *stream);
+
 // gconv_kernels.hip
 CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
                           int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

@@ -52,6 +52,7 @@ enum : int {
   kLayerNorm = 49,
   kGelu = 50,
   kAttention = 51,
+  kWindowAttention = 52,
   kPairTestGap = 1024,
 };
 
@@ -74,6 +75,7 @@ inline int GetLayerType(const std::string &t) {
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
       {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
       {"layer_norm", kLayerNorm}, {"gelu", kGelu}, {"attention", kAttention},
+      {"window_attention", kWindowAttention},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

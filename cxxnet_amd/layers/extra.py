@@ -1,6 +1,7 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
-ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu and attention.
+ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu, attention and
+window_attention.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
@@ -850,6 +851,102 @@ class AttentionLayer(Layer):
                         x.shape[0] // self.tokens, self.nhead, self._state(x), prop_grad, self.bf16_products)
 
 
+class WindowAttentionLayer(Layer):
+    """`window_attention` (type id 52) -- an extension, no reference counterpart: multi-head
+    self-attention inside non-overlapping ws x ws windows of a map, with Swin's cyclic shift, region
+    mask and learned relative position bias (Liu et al. 2021), 1 -> 1.  The input node
+    [B, 3 C, H, W] is the fused qkv map in `attention`'s channel layout (channel s C + h d + j is
+    component j of head h of q / k / v); the output node is [B, C, H, W].
+        nhead       required; d = C / nhead must be 32
+        window      required: ws, with ws^2 <= 64 and ws dividing H and W
+        shift       default 0; 0 <= shift < ws
+        init_sigma  default 0: the bias table starts at zero, else normal(0, init_sigma)
+    Window (Wy, Wx) holds the tokens t = wy ws + wx at rolled-frame coordinates y' = Wy ws + wy,
+    x' = Wx ws + wx, which sit at map position ((y' + shift) mod H, (x' + shift) mod W) -- Swin's
+    roll(-shift) followed by the partition -- and the output goes back to the same positions.  Per
+    sample, window and head: S_ij = q_i . k_j / sqrt(d) + bias[h][(wy_i - wy_j + ws - 1) (2 ws - 1) +
+    wx_i - wx_j + ws - 1]; key j is excluded for query i (probability exactly 0) when
+    (y'_i + shift >= H) != (y'_j + shift >= H) or the same test on x' and W differs; softmax in fp32,
+    O = P V, one rounding at the store.  The log-sum-exp of every row is kept
+    (ops.layer_ops.WAttnState).  Backward: dV, dS, dQ, dK as in `attention`, written into x.gdst
+    only with prop_grad (x.gdst may be x.data); gbias[h][r] += the sum of dS over the batch, the
+    windows and the pairs at relative index r, always.  qkv is read again, so the output node must
+    differ from the input.  The bias table ("wmat", (nhead, (2 ws - 1)^2), fp32, never rounded to
+    bf16) is the one tensor of the checkpoint."""
+    replay_audited = False  # (as attention)
+    type_name = "window_attention"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.nhead = self.window = self.shift = 0
+        self.init_sigma = 0.0
+        self._st = None
+        self.loaded = None
+        self.bf16_products = False  # torch path: round P and dS as the HIP kernels do (a test's measuring switch)
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name in ("nhead", "window", "shift"):
+            setattr(self, name, int(val))
+        elif name == "init_sigma":
+            self.init_sigma = float(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        who = "WindowAttentionLayer: "
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, who + "only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               who + "window_attention reads its input again in backward, so the output node must differ from the "
+               "input (no self-loop)")
+        _check(not nodes_in[0].is_mat(), who + "the input must be a map, not a matrix node")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], who + "padded-channel input is not supported")
+        _check(self.nhead > 0, who + "must set nhead")
+        b, c3, h, w = nodes_in[0].shape
+        _check(c3 % (3 * self.nhead) == 0, who + "%d input channels are not 3 x nhead = %d x a head width" % (c3, self.nhead))
+        self.channel = c3 // 3
+        _check(self.channel // self.nhead == 32,
+               who + "head width %d: the kernels serve 32" % (self.channel // self.nhead))
+        ws = self.window
+        _check(ws >= 1 and ws * ws <= 64, who + "window = %d: a window holds 1 to 64 tokens (window 1 to 8)" % ws)
+        _check(h % ws == 0 and w % ws == 0, who + "window = %d does not divide the %d x %d map" % (ws, h, w))
+        _check(0 <= self.shift < ws, who + "shift = %d: must be in 0 .. window - 1 = %d" % (self.shift, ws - 1))
+        nodes_out[0].set_shape(b, self.channel, h, w)
+        self.max_batch, self.hw = b, (h, w)
+
+        def init(t):
+            t.zero_()
+            if self.init_sigma > 0:  # conv's wmat initialiser at random_type = gaussian
+                from ..ops.layer_ops import rand_fill
+                rand_fill(t, int(torch.randint(0, 2**31 - 1, (1,), generator=self.ctx.gen).item()), "normal", 0.0,
+                          self.init_sigma)
+        self.params = [ParamSpec("wmat", (self.nhead, (2 * ws - 1) ** 2), init)]
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.WAttnState(self.max_batch, *self.hw, self.channel, self.nhead, self.window, self.shift,
+                                    x.device, torch.float64 if x.dtype == torch.float64 else torch.float32)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.wattn_forward(x, nodes_out[0].data.view(-1, self.channel), self.params[0].w,
+                        x.shape[0] // (self.hw[0] * self.hw[1]), self.nhead, self._state(x), self.bf16_products)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.wattn_backward(nodes_out[0].data.view(-1, self.channel), x, nodes_in[0].gdst.view(-1, 3 * self.channel),
+                         self.params[0].w, self.params[0].g, x.shape[0] // (self.hw[0] * self.hw[1]), self.nhead,
+                         self._state(x), prop_grad, self.bf16_products)
+
+    def save_model(self, fo: BinWriter):
+        fo.write_tensor(self.params[0].w)
+
+    def load_model(self, fi: BinReader):
+        self.loaded = [fi.read_tensor(2)]
+
+    def loaded_values(self):
+        return self.loaded
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -1171,6 +1268,7 @@ def _register():
     register(49, LayerNormLayer)
     register(50, GeluLayer)
     register(51, AttentionLayer)
+    register(52, WindowAttentionLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

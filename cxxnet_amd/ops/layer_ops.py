@@ -1,6 +1,6 @@
 """Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
 extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path,
-layer_norm, gelu, attention.
+layer_norm, gelu, attention, window_attention.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -439,6 +439,114 @@ def attn_backward(g, qkv, dqkv, B, nhead, st: AttnState, prop_grad: bool, bf16_p
     _flat_bf16(g, qkv, dqkv, who="attn_backward")
     native.check(_k().cxn_attn_bwd(qkv.data_ptr(), g.data_ptr(), st.lse2.data_ptr(), st.dsum.data_ptr(),
                                    dqkv.data_ptr(), st.dq.data_ptr(), B, T, C, nhead, _stream()), "attn_bwd")
+
+
+# ----------------------------------------------------------------------------- window attention
+class WAttnState:
+    """Per-layer device buffers of window_attention, sized once for the largest batch: the fp32
+    log-sum-exp of every softmax row, [B nhead H W] at the row's map position (lse2: the same in the
+    kernels' log2 units), and the slab workspace of the bias gradient
+    (csrc/kernels/wattn_kernels.hip).  A smaller batch uses their leading part."""
+
+    def __init__(self, max_batch, H, W, C, nhead, ws, shift, device, dtype=torch.float32):
+        self.geom = (int(H), int(W), int(ws), int(shift))
+        self.lse = torch.zeros(max_batch * nhead * H * W, dtype=dtype, device=device)  # (fp64: the torch path's tests)
+        self.lse2 = torch.zeros(max_batch * nhead * H * W, dtype=torch.float32, device=device)
+        self.ws = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_wattn_ws_floats(int(max_batch), int(H), int(W), int(C), int(nhead), int(ws), int(shift)))
+            self.ws = torch.zeros(max(n, 1), dtype=torch.float32, device=device)
+        self._index = None
+
+    def index(self, device):
+        """pos [nwin][n]: the map position y W + x of token t = wy ws + wx of every window; rel
+        [n][n]: the bias index of (query, key); on [nwin][n][n]: the key is attended (equal wrap
+        flags).  Index arithmetic on the map, computed once."""
+        if self._index is None:
+            H, W, ws, shift = self.geom
+            win = torch.arange((H // ws) * (W // ws), device=device)[:, None]
+            t = torch.arange(ws * ws, device=device)
+            wy, wx = t // ws, t % ws
+            yr, xr = win // (W // ws) * ws + wy + shift, win % (W // ws) * ws + wx + shift
+            fy, fx = yr >= H, xr >= W
+            pos = (yr % H) * W + xr % W
+            rel = (wy[:, None] - wy[None] + ws - 1) * (2 * ws - 1) + wx[:, None] - wx[None] + ws - 1
+            on = (fy[:, :, None] == fy[:, None, :]) & (fx[:, :, None] == fx[:, None, :])
+            self._index = pos, rel, on
+        return self._index
+
+
+def _wattn_logits(qkv, bias, B, nhead, st):
+    """the windows' q, k, v [B, nwin, nhead, n, d] gathered from qkv [B H W][3 C] and the masked,
+    biased logits [B, nwin, nhead, n, n], in qkv's precision (fp32 at least)"""
+    pos, rel, on = st.index(qkv.device)
+    d = qkv.shape[1] // (3 * nhead)
+    x = qkv if qkv.dtype == torch.float64 else qkv.float()
+    x = x.view(B, -1, 3, nhead, d)[:, pos].permute(3, 0, 1, 4, 2, 5)
+    q, k, v = x[0], x[1], x[2]
+    s = q @ k.transpose(-1, -2) / d ** 0.5 + bias.to(x.dtype)[:, rel]
+    return q, k, v, s.masked_fill(~on[:, None], float("-inf")), pos, rel
+
+
+def wattn_forward(qkv, out, bias, B, nhead, st: WAttnState, bf16_products=False):
+    """qkv [B H W][3 C] in attention's channel layout, out [B H W][C], bias [nhead][(2 ws - 1)^2]
+    fp32.  Per sample, window and head O = softmax(Q K^T / sqrt(d) + bias, keys across a wrap of the
+    cyclic shift excluded) V, written back to the tokens' map positions; st.lse receives every
+    row's log-sum-exp.  out must not alias qkv.  bf16_products: as attn_forward."""
+    H, W, ws, shift = st.geom
+    rows, C3 = qkv.shape
+    C = C3 // 3
+    if rows != B * H * W or B * nhead * H * W > st.lse.shape[0]:
+        raise ValueError("wattn_forward: %d rows at batch %d, state sized for %d" % (rows, B, st.lse.shape[0]))
+    if qkv.data_ptr() == out.data_ptr():
+        raise ValueError("wattn_forward: out must not alias qkv (backward reads qkv again)")
+    if not _native_t(qkv):
+        q, k, v, s, pos, _ = _wattn_logits(qkv, bias, B, nhead, st)
+        lse = torch.logsumexp(s, -1, keepdim=True)
+        st.lse[:B * nhead * H * W].view(B, nhead, H * W)[:, :, pos.reshape(-1)] = \
+            lse.permute(0, 2, 1, 3, 4).reshape(B, nhead, -1).to(st.lse.dtype)
+        p = torch.exp(s - lse)
+        o = (_bf16_round(p) if bf16_products else p) @ v
+        out.view(B, H * W, C)[:, pos.reshape(-1)] = o.permute(0, 1, 3, 2, 4).reshape(B, H * W, C).to(out.dtype)
+        return
+    _flat_bf16(qkv, out, who="wattn_forward")
+    native.check(_k().cxn_wattn_fwd(qkv.data_ptr(), out.data_ptr(), bias.data_ptr(), st.lse.data_ptr(),
+                                    st.lse2.data_ptr(), B, H, W, C, nhead, ws, shift, _stream()), "wattn_fwd")
+
+
+def wattn_backward(g, qkv, dqkv, bias, gbias, B, nhead, st: WAttnState, prop_grad: bool, bf16_products=False):
+    """g [B H W][C] = dO.  With P of the last forward, dP = dO V^T, D_i = sum_j P_ij dP_ij and
+    dS = P (dP - D): gbias[h][r] += sum of dS over the batch, the windows and the pairs at relative
+    index r (always), and with prop_grad dV = P^T dO, dQ = dS K / sqrt(d), dK = dS^T Q / sqrt(d) into
+    dqkv [B H W][3 C], which may be qkv.  bf16_products: as attn_backward (gbias takes the unrounded
+    dS either way, as in the kernels)."""
+    H, W, ws, shift = st.geom
+    rows, C3 = qkv.shape
+    C = C3 // 3
+    if not _native_t(g):
+        q, k, v, s, pos, rel = _wattn_logits(qkv, bias, B, nhead, st)
+        n, d = ws * ws, C // nhead
+        sc = 1.0 / d ** 0.5
+        do = (g if g.dtype == torch.float64 else g.float()).view(B, H * W, nhead, d)[:, pos].permute(0, 1, 3, 2, 4)
+        lse = st.lse[:B * nhead * H * W].view(B, nhead, H * W)[:, :, pos].permute(0, 2, 1, 3).unsqueeze(-1)
+        p = torch.exp(s - lse.to(s.dtype))
+        dp = do @ v.transpose(-1, -2)
+        ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+        gbias.index_add_(1, rel.reshape(-1), ds.sum((0, 1)).reshape(nhead, n * n).to(gbias.dtype))
+        if not prop_grad:
+            return
+        if bf16_products:
+            p, ds = _bf16_round(p), _bf16_round(ds)
+        grads = torch.stack([ds @ k * sc, ds.transpose(-1, -2) @ q * sc, p.transpose(-1, -2) @ do])
+        dqkv.view(B, H * W, 3, nhead, d)[:, pos.reshape(-1)] = \
+            grads.permute(1, 2, 4, 0, 3, 5).reshape(B, H * W, 3, nhead, d).to(dqkv.dtype)
+        return
+    _flat_bf16(g, qkv, who="wattn_backward")
+    if prop_grad:
+        _flat_bf16(dqkv, who="wattn_backward")
+    native.check(_k().cxn_wattn_bwd(qkv.data_ptr(), g.data_ptr(), bias.data_ptr(), st.lse2.data_ptr(),
+                                    dqkv.data_ptr() if prop_grad else None, gbias.data_ptr(), st.ws.data_ptr(),
+                                    st.ws.numel(), B, H, W, C, nhead, ws, shift, _stream()), "wattn_bwd")
 
 
 # ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
