@@ -1,7 +1,8 @@
 """Sibling 1x1 convs of GoogLeNet's inception modules as one GEMM per direction
 (NeuralNet._fuse_siblings, ops.gemm.conv_forward_split) against the unfused layers
 (CXXNET_FUSE_SIBLINGS=0): every module fused, the same training step to bf16 accuracy, and the
-two-destination GEMM against fp32 torch."""
+two-destination GEMM against fp32 torch.  Per-element coverage of the same fusions on a tiny
+net: tests/test_net_audit_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
