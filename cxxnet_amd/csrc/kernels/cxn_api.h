@@ -298,6 +298,14 @@ CXN_API int cxn_wattn_bwd(const void *qkv, const void *dout, const float *bias, 
                           float *gbias, float *slabs, long ws_floats, long B, int H, int W, int C, int nhead, int ws,
                           int shift, void *stream);
 
+// kvattn_kernels.hip
+CXN_API int cxn_kvattn_tile(int d, long Tq, int *rows_per_tile, int *splits);
+CXN_API long cxn_kvattn_ws_floats(long B, long Tq, long Tk, int C, int nhead);
+CXN_API int cxn_kvattn_fwd(const void *q, const void *kv, void *out, float *lse, long B, long Tq, long Tk, int C,
+                           int nhead, void *stream);
+CXN_API int cxn_kvattn_bwd(const void *q, const void *kv, const void *dout, void *dq, void *dkv, float *slabs,
+                           long ws_floats, long B, long Tq, long Tk, int C, int nhead, void *stream);
+
 // gconv_kernels.hip
 CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
                           int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

@@ -53,6 +53,7 @@ enum : int {
   kGelu = 50,
   kAttention = 51,
   kWindowAttention = 52,
+  kKVAttention = 53,
   kPairTestGap = 1024,
 };
 
@@ -75,7 +76,7 @@ inline int GetLayerType(const std::string &t) {
       {"relu6", kRelu6}, {"hsigmoid", kHSigmoid}, {"hswish", kHSwish},
       {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
       {"layer_norm", kLayerNorm}, {"gelu", kGelu}, {"attention", kAttention},
-      {"window_attention", kWindowAttention},
+      {"window_attention", kWindowAttention}, {"kv_attention", kKVAttention},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

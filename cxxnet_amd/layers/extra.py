@@ -1,7 +1,7 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
-ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu, attention and
-window_attention.
+ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu, attention,
+window_attention and kv_attention.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
@@ -947,6 +947,85 @@ class WindowAttentionLayer(Layer):
         return self.loaded
 
 
+class KVAttentionLayer(Layer):
+    """`kv_attention` (type id 53) -- an extension, no reference counterpart: multi-head attention
+    of the positions of one map over a short key / value set taken from another node, 2 -> 1, no
+    parameters: `layer[q,kv->o] = kv_attention`, the spatial-reduction attention of PVT / PVTv2.
+    q [B, C, H, W] is read as rows [B Tq][C], Tq = H W, channel h d + j = component j of head h;
+    kv [B, 2 C, Hk, Wk] as rows [B Tk][2 C], Tk = Hk Wk, channel s C + h d + j with s = 0 for k and
+    1 for v -- what a fused kv projection followed by reshape(B, Tk, 2, nhead, d) yields, `attention`'s
+    convention.  Either may be a matrix node (T = 1).  The output node is shaped like q.
+        nhead       required; d = C / nhead must be 32 or 64, 1 <= Tk <= 64, 1 <= Tq <= 16384
+    Forward and backward are `attention`'s formulas per sample and head with the keys and values of
+    kv: S = Q K^T / sqrt(d), P = softmax in fp32, O = P V, one rounding at the store; the log-sum-exp
+    of every row is kept (ops.layer_ops.KVAttnState).  With g = dO held by the output node:
+    dP = dO V^T, D = sum_j P dP, dV = P^T dO, dS = P (dP - D), dQ = dS K / sqrt(d) into q.gdst,
+    dK = dS^T Q / sqrt(d) and dV into kv.gdst as [B Tk][2 C], only with prop_grad.  Both inputs are
+    read again in backward, so the three nodes must be distinct; q.gdst may be q.data and kv.gdst
+    may be kv.data.  Nothing to save in a checkpoint."""
+    replay_audited = False  # (as attention)
+    type_name = "kv_attention"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.nhead = 0
+        self._st = None
+        self.bf16_products = False  # torch path: round P and dS as the HIP kernels do (a test's measuring switch)
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name == "nhead":
+            self.nhead = int(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        who = "KVAttentionLayer: "
+        _check(len(nodes_in) == 2 and len(nodes_out) == 1, who + "only support 2-1 connection")
+        q, kv = nodes_in
+        out = nodes_out[0]
+        _check(q is not kv and out is not q and out is not kv,
+               who + "kv_attention reads both inputs again in backward, so q, kv and the output must be three "
+               "distinct nodes")
+        for n in nodes_in:
+            _check(n.cp == n.shape[1], who + "padded-channel input is not supported")
+        _check(self.nhead > 0, who + "must set nhead")
+        b, c, h, w = q.shape
+        self.channel = _num_feat(q)
+        self.tq = c * h * w // self.channel
+        c2 = _num_feat(kv)
+        _check(kv.shape[0] == b and c2 == 2 * self.channel,
+               who + "kv has %d channels at batch %d: q's batch %d and 2 x its %d channels expected" %
+               (c2, kv.shape[0], b, self.channel))
+        self.tk = kv.shape[1] * kv.shape[2] * kv.shape[3] // c2
+        _check(self.channel % self.nhead == 0,
+               who + "%d channels are not nhead = %d x a head width" % (self.channel, self.nhead))
+        d = self.channel // self.nhead
+        _check(d in (32, 64), who + "head width %d: the kernels serve 32 and 64" % d)
+        _check(1 <= self.tk <= 64, who + "%d key positions: the kernels serve 1 to 64" % self.tk)
+        _check(1 <= self.tq <= 16384, who + "%d query positions: the kernels serve 1 to 16384" % self.tq)
+        out.set_shape(*q.shape)
+        self.max_batch = b
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.KVAttnState(self.max_batch, self.tq, self.tk, self.channel, self.nhead, x.device,
+                                     torch.float64 if x.dtype == torch.float64 else torch.float32)
+        return self._st
+
+    def _views(self, q, kv):
+        return q.view(-1, self.channel), kv.view(-1, 2 * self.channel)
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        q, kv = self._views(nodes_in[0].data, nodes_in[1].data)
+        L.kvattn_forward(q, kv, nodes_out[0].data.view(-1, self.channel), q.shape[0] // self.tq, self.nhead,
+                         self._state(q), self.bf16_products)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        q, kv = self._views(nodes_in[0].data, nodes_in[1].data)
+        dq, dkv = self._views(nodes_in[0].gdst, nodes_in[1].gdst)
+        L.kvattn_backward(nodes_out[0].data.view(-1, self.channel), q, kv, dq, dkv, q.shape[0] // self.tq,
+                          self.nhead, self._state(q), prop_grad, self.bf16_products)
+
+
 class PReluLayer(Layer):
     """`prelu` -- reference src/layer/prelu_layer-inl.hpp:48-173 (per-channel slope
     clamped to [0,1], optional multiplicative train-time noise `random`; the slope is
@@ -1269,6 +1348,7 @@ def _register():
     register(50, GeluLayer)
     register(51, AttentionLayer)
     register(52, WindowAttentionLayer)
+    register(53, KVAttentionLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -3,6 +3,7 @@ ResNet-18-GN (group_norm in place of batch_norm_ma), SE-ResNet-18, MobileNet-v1,
 EfficientNet-B0 (silu, drop_path), ResNeXt-50 32x4d, ConvNeXt-T (7x7 depthwise, layer_norm, gelu),
 CPVT-Small (attention, a depthwise position encoding, global average pooling),
 Swin-T (window_attention: shifted 7x7 windows with a relative position bias),
+PVTv2-b1 (kv_attention over a spatially reduced map, overlapping patch embeddings),
 MNIST MLP/conv, Kaggle-bowl convnet) and helpers
 to load them."""
 from __future__ import annotations

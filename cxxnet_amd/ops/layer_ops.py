@@ -1,6 +1,6 @@
 """Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
 extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path,
-layer_norm, gelu, attention, window_attention.
+layer_norm, gelu, attention, window_attention, kv_attention.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -547,6 +547,95 @@ def wattn_backward(g, qkv, dqkv, bias, gbias, B, nhead, st: WAttnState, prop_gra
     native.check(_k().cxn_wattn_bwd(qkv.data_ptr(), g.data_ptr(), bias.data_ptr(), st.lse2.data_ptr(),
                                     dqkv.data_ptr() if prop_grad else None, gbias.data_ptr(), st.ws.data_ptr(),
                                     st.ws.numel(), B, H, W, C, nhead, ws, shift, _stream()), "wattn_bwd")
+
+
+# ----------------------------------------------------------------------------- kv attention
+class KVAttnState:
+    """Per-layer device buffers of kv_attention, sized once for the largest batch: the fp32
+    log-sum-exp of every query row, [B nhead Tq] (the torch path's backward reads it; the kernels'
+    backward normalises its own softmax again, see csrc/kernels/kvattn_kernels.hip), and the slab
+    workspace of dK / dV when the queries are split (csrc/kernels/kvattn_kernels.hip).  A
+    smaller batch uses their leading part."""
+
+    def __init__(self, max_batch, Tq, Tk, C, nhead, device, dtype=torch.float32):
+        self.lse = torch.zeros(max_batch * nhead * Tq, dtype=dtype, device=device)  # (fp64: the torch path's tests)
+        self.ws = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_kvattn_ws_floats(int(max_batch), int(Tq), int(Tk), int(C), int(nhead)))
+            if n < 0:
+                raise ValueError("KVAttnState: Tq %d, Tk %d, C %d, nhead %d is not served" % (Tq, Tk, C, nhead))
+            self.ws = torch.zeros(max(n, 4), dtype=torch.float32, device=device)
+
+
+def kvattn_tile(d: int, Tq: int):
+    """(queries per tile, splits of the backward over Tq queries) of the kv_attention kernels."""
+    import ctypes
+    r, s = ctypes.c_int(0), ctypes.c_int(0)
+    native.check(_k().cxn_kvattn_tile(int(d), int(Tq), ctypes.byref(r), ctypes.byref(s)), "kvattn_tile")
+    return r.value, s.value
+
+
+def _kvattn_heads(q, kv, B, nhead):
+    """q [B, nhead, Tq, d] and k, v [B, nhead, Tk, d] of q [B Tq][C] and kv [B Tk][2 C], in their
+    precision (fp32 at least)"""
+    C = q.shape[1]
+    up = (lambda t: t) if q.dtype == torch.float64 else (lambda t: t.float())
+    x = up(kv).view(B, -1, 2, nhead, C // nhead).permute(2, 0, 3, 1, 4)
+    return up(q).view(B, -1, nhead, C // nhead).permute(0, 2, 1, 3), x[0], x[1]
+
+
+def kvattn_forward(q, kv, out, B, nhead, st: KVAttnState, bf16_products=False):
+    """q [B Tq][C] (channel h d + j: component j of head h), kv [B Tk][2 C] (channel s C + h d + j,
+    s = 0 for k and 1 for v), out [B Tq][C].  Per sample and head O = softmax(Q K^T / sqrt(d)) V with
+    the softmax in fp32; st.lse receives every row's log-sum-exp.  out must alias neither input.
+    bf16_products: as attn_forward."""
+    (rows, C), Tk = q.shape, kv.shape[0] // B
+    Tq = rows // B
+    if B * nhead * Tq > st.lse.shape[0]:
+        raise ValueError("kvattn_forward: batch %d, state sized for %d rows" % (B, st.lse.shape[0]))
+    if out.data_ptr() in (q.data_ptr(), kv.data_ptr()):
+        raise ValueError("kvattn_forward: out must not alias q or kv (backward reads them again)")
+    if not _native_t(q):
+        qh, k, v = _kvattn_heads(q, kv, B, nhead)
+        s = qh @ k.transpose(-1, -2) / (C // nhead) ** 0.5
+        lse = torch.logsumexp(s, -1, keepdim=True)
+        st.lse[:B * nhead * Tq].copy_(lse.reshape(-1))
+        p = torch.exp(s - lse)
+        o = (_bf16_round(p) if bf16_products else p) @ v
+        out.copy_(o.permute(0, 2, 1, 3).reshape(rows, C))
+        return
+    _flat_bf16(q, kv, out, who="kvattn_forward")
+    native.check(_k().cxn_kvattn_fwd(q.data_ptr(), kv.data_ptr(), out.data_ptr(), st.lse.data_ptr(), B, Tq, Tk,
+                                     C, nhead, _stream()), "kvattn_fwd")
+
+
+def kvattn_backward(g, q, kv, dq, dkv, B, nhead, st: KVAttnState, prop_grad: bool, bf16_products=False):
+    """g [B Tq][C] = dO.  With P = exp(S - lse) of the last forward, dP = dO V^T and
+    D_i = sum_j P_ij dP_ij: dV = P^T dO, dS = P (dP - D), dQ = dS K / sqrt(d) into dq [B Tq][C], which
+    may be q, and dK = dS^T Q / sqrt(d) with dV into dkv [B Tk][2 C], which may be kv.  Without
+    prop_grad nothing is computed or written.  bf16_products: as attn_backward."""
+    if not prop_grad:
+        return
+    (rows, C), Tk = q.shape, kv.shape[0] // B
+    Tq = rows // B
+    if not _native_t(g):
+        qh, k, v = _kvattn_heads(q, kv, B, nhead)
+        sc = 1.0 / (C // nhead) ** 0.5
+        do = (g if g.dtype == torch.float64 else g.float()).view(B, Tq, nhead, C // nhead).permute(0, 2, 1, 3)
+        p = torch.exp(qh @ k.transpose(-1, -2) * sc - st.lse[:B * nhead * Tq].view(B, nhead, Tq, 1).to(qh.dtype))
+        dp = do @ v.transpose(-1, -2)
+        ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+        if bf16_products:
+            p, ds = _bf16_round(p), _bf16_round(ds)
+        gq = ds @ k * sc
+        gkv = torch.stack([ds.transpose(-1, -2) @ qh * sc, p.transpose(-1, -2) @ do])
+        dq.copy_(gq.permute(0, 2, 1, 3).reshape(rows, C))
+        dkv.copy_(gkv.permute(1, 3, 0, 2, 4).reshape(B * Tk, 2 * C))
+        return
+    _flat_bf16(g, q, kv, dq, dkv, who="kvattn_backward")
+    native.check(_k().cxn_kvattn_bwd(q.data_ptr(), kv.data_ptr(), g.data_ptr(), dq.data_ptr(),
+                                     dkv.data_ptr(), st.ws.data_ptr(), st.ws.numel(), B, Tq, Tk, C, nhead, _stream()),
+                 "kvattn_bwd")
 
 
 # ----------------------------------------------------------------------------- add (element-wise sum, fused relu)
