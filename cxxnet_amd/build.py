@@ -90,6 +90,7 @@ FILE_FLAGS = {
     "gelu_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "wattn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "nattn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "kvattn_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 

@@ -1,6 +1,8 @@
 // What the attention kernel files share (attn_kernels.hip, kvattn_kernels.hip): the swizzled
 // [64][D] bf16 LDS tile, its LDS-DMA staging from strided rows, the row-major and transposed MFMA
-// operand fragments, and the small register helpers around the compiler-builtin MFMA.  See
+// operand fragments, and the small register helpers around the compiler-builtin MFMA; and, in
+// namespace row64, the [rows][32] tile of wattn_kernels.hip and nattn_kernels.hip with the swizzle
+// a 64-byte row needs (wattn_kernels.hip's header derives it).  See
 // attn_kernels.hip's header for why the products are computed transposed and why the MFMAs are the
 // builtin and not gfx950_prims.h's asm forms.
 #pragma once
@@ -95,6 +97,31 @@ __device__ __forceinline__ void store_row(bf16_t *row, int g, const f32x4 (&acc)
 __device__ __forceinline__ uint32_t lds_base(const char *smem) {
   return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_void *)smem)));
 }
+
+// The [rows][32] bf16 tile with 64-byte rows.  Unit lc of row r lives at physical unit lc ^ swz(r),
+// swz(r) = bit 2 of r as bit 1, bit 3 of r as bit 0; the argument needs 16 (row_frag) or 8 (tr_frag)
+// consecutive rows, not an aligned first row.
+namespace row64 {
+
+__device__ __forceinline__ int swz(int r) { return ((r >> 1) & 2) | ((r >> 3) & 1); }
+
+// byte address of 16-byte unit lc of row r
+__device__ __forceinline__ int tile_addr(int r, int lc) { return r * 64 + ((lc ^ swz(r)) << 4); }
+
+// row-major operand fragment: row r, columns 8 g ..
+__device__ __forceinline__ bf16x8 row_frag(const char *tile, int r, int g) {
+  return *reinterpret_cast<const bf16x8 *>(tile + tile_addr(r, g));
+}
+
+// transposed operand fragment: lane (i, g) gets column 16 dt + i of rows rb + 4 g + j (slots 0..3)
+// and rb + 16 + 4 g + j (slots 4..7) -- the order in which a lane holds two 16 x 16 result tiles
+__device__ __forceinline__ bf16x8 tr_frag(const char *tile, int rb, int dt, int i, int g) {
+  const int r = rb + 4 * g + (i >> 2);
+  const char *p = tile + tile_addr(r, 2 * dt + ((i & 3) >> 1)) + (i & 1) * 8;
+  return frag_tr(p, p + 16 * 64);  // (row r + 16 has row r's swizzle)
+}
+
+}  // namespace row64
 
 }  // namespace attn
 }  // namespace cxg

@@ -306,6 +306,14 @@ CXN_API int cxn_kvattn_fwd(const void *q, const void *kv, void *out, float *lse,
 CXN_API int cxn_kvattn_bwd(const void *q, const void *kv, const void *dout, void *dq, void *dkv, float *slabs,
                            long ws_floats, long B, long Tq, long Tk, int C, int nhead, void *stream);
 
+// nattn_kernels.hip
+CXN_API long cxn_nattn_ws_floats(long B, int H, int W, int C, int nhead, int kernel);
+CXN_API int cxn_nattn_fwd(const void *qkv, void *out, const float *bias, float *lse, float *lse2, long B, int H,
+                          int W, int C, int nhead, int kernel, void *stream);
+CXN_API int cxn_nattn_bwd(const void *qkv, const void *dout, const float *bias, const float *lse2, float *dsum,
+                          void *dqkv, void *dq_stage, float *gbias, float *slabs, long ws_floats, long B, int H, int W,
+                          int C, int nhead, int kernel, void *stream);
+
 // gconv_kernels.hip
 CXN_API int cxn_gconv_fwd(const void *x, long xs, const void *w, const float *bias, void *y, long ys, int N, int H,
                           int W, int C, int Cout, int groups, int KH, int KW, int stride, int pad_y, int pad_x,

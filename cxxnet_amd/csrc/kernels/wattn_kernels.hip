@@ -65,9 +65,10 @@
 //
 // Hazards.  P and dS are VALU results feeding MFMA operands: every MFMA is the compiler builtin
 // (see attn_kernels.hip).  The DMAs are the asm form; completion is vmcnt(0) plus a block barrier.
-#include "gfx950_prims.h"
+#include "attn_tile.h"
 
 using namespace cxg;
+using namespace cxg::attn::row64;  // swz, tile_addr, row_frag, tr_frag of the [64][32] tile
 
 namespace {
 
@@ -89,24 +90,6 @@ struct WArgs {
   long items, per;                   // (sample, window) items; backward: items per run
   float sc2, scale;                  // log2e / sqrt(d), 1 / sqrt(d)
 };
-
-__device__ __forceinline__ int swz(int r) { return ((r >> 1) & 2) | ((r >> 3) & 1); }
-
-// byte address of 16-byte unit lc of row r in a [64][32] bf16 tile
-__device__ __forceinline__ int tile_addr(int r, int lc) { return r * (D * 2) + ((lc ^ swz(r)) << 4); }
-
-// row-major operand fragment: row r, columns 8 g ..
-__device__ __forceinline__ bf16x8 row_frag(const char *tile, int r, int g) {
-  return *reinterpret_cast<const bf16x8 *>(tile + tile_addr(r, g));
-}
-
-// transposed operand fragment: lane (i, g) gets column 16 dt + i of rows rb + 4 g + j (slots 0..3)
-// and rb + 16 + 4 g + j (slots 4..7) -- the order in which a lane holds two 16 x 16 result tiles
-__device__ __forceinline__ bf16x8 tr_frag(const char *tile, int rb, int dt, int i, int g) {
-  const int r = rb + 4 * g + (i >> 2);
-  const char *p = tile + tile_addr(r, 2 * dt + ((i & 3) >> 1)) + (i & 1) * 8;
-  return frag_tr(p, p + 16 * D * 2);  // (row r + 16 has row r's swizzle)
-}
 
 __device__ __forceinline__ f32x4 mma(const bf16x8 &a, const bf16x8 &b, const f32x4 &c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);

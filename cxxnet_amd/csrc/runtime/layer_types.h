@@ -54,6 +54,7 @@ enum : int {
   kAttention = 51,
   kWindowAttention = 52,
   kKVAttention = 53,
+  kNeighborhoodAttention = 54,
   kPairTestGap = 1024,
 };
 
@@ -77,6 +78,7 @@ inline int GetLayerType(const std::string &t) {
       {"group_norm", kGroupNorm}, {"silu", kSilu}, {"drop_path", kDropPath},
       {"layer_norm", kLayerNorm}, {"gelu", kGelu}, {"attention", kAttention},
       {"window_attention", kWindowAttention}, {"kv_attention", kKVAttention},
+      {"neighborhood_attention", kNeighborhoodAttention},
       {"caffe", kCaffe},
   };
   for (const auto &e : table) {

@@ -1,7 +1,7 @@
 """Remaining reference layers: bias, split, concat, ch_concat, batch_norm, prelu,
 insanity, insanity_max_pooling, fixconn, pairtest -- and the extensions batch_norm_ma, add,
 ch_scale, relu6 / hsigmoid / hswish, group_norm, silu, drop_path, layer_norm, gelu, attention,
-window_attention and kv_attention.
+window_attention, kv_attention and neighborhood_attention.
 
 On the GPU every one of them runs hand-written HIP kernels: batch_norm / prelu / insanity /
 insanity_max_pooling in csrc/kernels/layer_kernels.hip (ops/layer_ops.py), batch_norm_ma in
@@ -947,6 +947,98 @@ class WindowAttentionLayer(Layer):
         return self.loaded
 
 
+class NeighborhoodAttentionLayer(Layer):
+    """`neighborhood_attention` (type id 54) -- an extension, no reference counterpart: multi-head
+    attention of every pixel of a map over the k x k pixels around it, with a learned relative
+    position bias (NAT, Hassani et al. 2023), 1 -> 1.  The input node [B, 3 C, H, W] is the fused qkv
+    map in `attention`'s channel layout (channel s C + h d + j is component j of head h of q / k /
+    v); the output node is [B, C, H, W].
+        nhead       required; d = C / nhead must be 32
+        kernel      required: k = 3, 5 or 7, with H >= k and W >= k (no dilation)
+        init_sigma  default 0: the bias table starts at zero, else normal(0, init_sigma)
+    The query at (y, x) has the k^2 keys (y', x') with sy <= y' < sy + k and sx <= x' < sx + k,
+    sy = clamp(y - k // 2, 0, H - k), sx = clamp(x - k // 2, 0, W - k): NAT's clamped neighbourhood --
+    a border query looks further inward, nothing is zero-padded.  Per sample and head:
+    S_ij = q_i . k_j / sqrt(d) + bias[h][(y' - y + k - 1) (2 k - 1) + x' - x + k - 1]; softmax over the
+    k^2 keys in fp32, O = P V, one rounding at the store.  The log-sum-exp of every row is kept
+    (ops.layer_ops.NAttnState).  Backward: dV, dS, dQ, dK as in `attention` restricted to the
+    neighbourhoods, written into x.gdst only with prop_grad (x.gdst may be x.data); gbias[h][r] += the
+    sum of dS over the batch and the (query, key) pairs at relative index r, always.  qkv is read
+    again, so the output node must differ from the input.  The bias table ("wmat",
+    (nhead, (2 k - 1)^2), fp32, never rounded to bf16) is the one tensor of the checkpoint."""
+    replay_audited = False  # (as attention)
+    type_name = "neighborhood_attention"
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.nhead = self.kernel = 0
+        self.init_sigma = 0.0
+        self._st = None
+        self.loaded = None
+        self.bf16_products = False  # torch path: round P and dS as the HIP kernels do (a test's measuring switch)
+
+    def set_param(self, name, val):
+        super().set_param(name, val)
+        if name in ("nhead", "kernel"):
+            setattr(self, name, int(val))
+        elif name == "init_sigma":
+            self.init_sigma = float(val)
+
+    def init_connection(self, nodes_in, nodes_out):
+        who = "NeighborhoodAttentionLayer: "
+        _check(len(nodes_in) == 1 and len(nodes_out) == 1, who + "only support 1-1 connection")
+        _check(nodes_in[0] is not nodes_out[0],
+               who + "neighborhood_attention reads its input again in backward, so the output node must differ from "
+               "the input (no self-loop)")
+        _check(not nodes_in[0].is_mat(), who + "the input must be a map, not a matrix node")
+        _check(nodes_in[0].cp == nodes_in[0].shape[1], who + "padded-channel input is not supported")
+        _check(self.nhead > 0, who + "must set nhead")
+        b, c3, h, w = nodes_in[0].shape
+        _check(c3 % (3 * self.nhead) == 0, who + "%d input channels are not 3 x nhead = %d x a head width" % (c3, self.nhead))
+        self.channel = c3 // 3
+        _check(self.channel // self.nhead == 32,
+               who + "head width %d: the kernels serve 32" % (self.channel // self.nhead))
+        k = self.kernel
+        _check(k in (3, 5, 7), who + "kernel = %d: must be odd, 3 to 7" % k)
+        _check(h >= k and w >= k, who + "kernel = %d does not fit the %d x %d map" % (k, h, w))
+        nodes_out[0].set_shape(b, self.channel, h, w)
+        self.max_batch, self.hw = b, (h, w)
+
+        def init(t):
+            t.zero_()
+            if self.init_sigma > 0:  # conv's wmat initialiser at random_type = gaussian
+                from ..ops.layer_ops import rand_fill
+                rand_fill(t, int(torch.randint(0, 2**31 - 1, (1,), generator=self.ctx.gen).item()), "normal", 0.0,
+                          self.init_sigma)
+        self.params = [ParamSpec("wmat", (self.nhead, (2 * k - 1) ** 2), init)]
+
+    def _state(self, x):
+        if self._st is None:  # once, for the largest batch
+            self._st = L.NAttnState(self.max_batch, *self.hw, self.channel, self.nhead, self.kernel, x.device,
+                                    torch.float64 if x.dtype == torch.float64 else torch.float32)
+        return self._st
+
+    def forward(self, is_train, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.nattn_forward(x, nodes_out[0].data.view(-1, self.channel), self.params[0].w,
+                        x.shape[0] // (self.hw[0] * self.hw[1]), self.nhead, self._state(x), self.bf16_products)
+
+    def backprop(self, prop_grad, nodes_in, nodes_out):
+        x = nodes_in[0].data.view(-1, 3 * self.channel)
+        L.nattn_backward(nodes_out[0].data.view(-1, self.channel), x, nodes_in[0].gdst.view(-1, 3 * self.channel),
+                         self.params[0].w, self.params[0].g, x.shape[0] // (self.hw[0] * self.hw[1]), self.nhead,
+                         self._state(x), prop_grad, self.bf16_products)
+
+    def save_model(self, fo: BinWriter):
+        fo.write_tensor(self.params[0].w)
+
+    def load_model(self, fi: BinReader):
+        self.loaded = [fi.read_tensor(2)]
+
+    def loaded_values(self):
+        return self.loaded
+
+
 class KVAttentionLayer(Layer):
     """`kv_attention` (type id 53) -- an extension, no reference counterpart: multi-head attention
     of the positions of one map over a short key / value set taken from another node, 2 -> 1, no
@@ -1349,6 +1441,7 @@ def _register():
     register(51, AttentionLayer)
     register(52, WindowAttentionLayer)
     register(53, KVAttentionLayer)
+    register(54, NeighborhoodAttentionLayer)
     register(29, PReluLayer)
     register(24, InsanityLayer)
     register(25, InsanityPoolingLayer)

@@ -4,6 +4,7 @@ EfficientNet-B0 (silu, drop_path), ResNeXt-50 32x4d, ConvNeXt-T (7x7 depthwise, 
 CPVT-Small (attention, a depthwise position encoding, global average pooling),
 Swin-T (window_attention: shifted 7x7 windows with a relative position bias),
 PVTv2-b1 (kv_attention over a spatially reduced map, overlapping patch embeddings),
+NAT-Mini (neighborhood_attention: every pixel over its clamped 7x7 neighbourhood),
 MNIST MLP/conv, Kaggle-bowl convnet) and helpers
 to load them."""
 from __future__ import annotations

@@ -1,6 +1,6 @@
 """Ops of the less common layers: batch_norm, prelu, insanity, insanity_max_pooling, and of the
 extensions batch_norm_ma, group_norm, add, ch_scale, relu6 / hsigmoid / hswish, silu, drop_path,
-layer_norm, gelu, attention, window_attention, kv_attention.
+layer_norm, gelu, attention, window_attention, kv_attention, neighborhood_attention.
 
 GPU: csrc/kernels/layer_kernels.hip.  CPU: the same formulas in fp32 torch, with the SAME
 counter-hash random draws as the kernels (element index of the NHWC buffer, seed
@@ -547,6 +547,127 @@ def wattn_backward(g, qkv, dqkv, bias, gbias, B, nhead, st: WAttnState, prop_gra
     native.check(_k().cxn_wattn_bwd(qkv.data_ptr(), g.data_ptr(), bias.data_ptr(), st.lse2.data_ptr(),
                                     dqkv.data_ptr() if prop_grad else None, gbias.data_ptr(), st.ws.data_ptr(),
                                     st.ws.numel(), B, H, W, C, nhead, ws, shift, _stream()), "wattn_bwd")
+
+
+# ----------------------------------------------------------------------------- neighborhood attention
+class NAttnState:
+    """Per-layer device buffers of neighborhood_attention, sized once for the largest batch: the
+    fp32 log-sum-exp of every softmax row, [B nhead H W] (lse2: the same in the kernels' log2
+    units), the backward's row term D, the [B H W][C] staging buffer dQ passes through when the
+    gradient overwrites qkv in place (allocated by the first such call), and the slab workspace of
+    the bias gradient, sized for every batch up to the largest (csrc/kernels/nattn_kernels.hip).  A
+    smaller batch uses their leading part."""
+
+    def __init__(self, max_batch, H, W, C, nhead, kernel, device, dtype=torch.float32):
+        self.geom = (int(H), int(W), int(kernel))
+        n = max_batch * nhead * H * W
+        self.lse = torch.zeros(n, dtype=dtype, device=device)  # (fp64: the torch path's tests)
+        self.lse2 = torch.zeros(n, dtype=torch.float32, device=device)
+        self.dsum = torch.zeros(n, dtype=torch.float32, device=device)
+        self.ws = self.dq = None
+        if torch.device(device).type == "cuda":
+            n = int(_k().cxn_nattn_ws_floats(int(max_batch), int(H), int(W), int(C), int(nhead), int(kernel)))
+            self.ws = torch.zeros(max(n, 1), dtype=torch.float32, device=device)
+        self._dq_shape = (max_batch * H * W, C)
+        self._index = None
+
+    def stage(self, device):
+        """the dQ staging buffer of an in-place backward"""
+        if self.dq is None:
+            self.dq = torch.zeros(self._dq_shape, dtype=torch.bfloat16, device=device)
+        return self.dq
+
+    def index(self, device):
+        """nbr [H W][k k]: the map positions y' W + x' of the keys of every query, NAT's clamped
+        neighbourhood (rows clamp(y - k // 2, 0, H - k) .., columns likewise); rel [H W][k k]: their
+        bias indices (y' - y + k - 1) (2 k - 1) + x' - x + k - 1.  Computed once."""
+        if self._index is None:
+            H, W, k = self.geom
+            ys, xs, kk = torch.arange(H, device=device), torch.arange(W, device=device), torch.arange(k, device=device)
+            ky = (ys - k // 2).clamp(0, H - k)[:, None] + kk  # [H, k]
+            kx = (xs - k // 2).clamp(0, W - k)[:, None] + kk  # [W, k]
+            nbr = ky[:, None, :, None] * W + kx[None, :, None, :]
+            rel = (ky - ys[:, None] + k - 1)[:, None, :, None] * (2 * k - 1) + (kx - xs[:, None] + k - 1)[None, :, None, :]
+            self._index = nbr.reshape(H * W, k * k), rel.reshape(H * W, k * k)
+        return self._index
+
+
+def _nattn_logits(qkv, bias, B, nhead, st):
+    """q [B, HW, nhead, d], the gathered k and v [B, HW, k k, nhead, d] of qkv [B H W][3 C] and the
+    biased logits [B, nhead, HW, k k], in qkv's precision (fp32 at least)"""
+    nbr, rel = st.index(qkv.device)
+    d = qkv.shape[1] // (3 * nhead)
+    x = (qkv if qkv.dtype == torch.float64 else qkv.float()).view(B, -1, 3, nhead, d)
+    q, k, v = x[:, :, 0], x[:, :, 1][:, nbr], x[:, :, 2][:, nbr]
+    s = torch.einsum("bphd,bpjhd->bhpj", q, k) / d ** 0.5 + bias.to(x.dtype)[:, rel]
+    return q, k, v, s, nbr, rel
+
+
+def nattn_forward(qkv, out, bias, B, nhead, st: NAttnState, bf16_products=False):
+    """qkv [B H W][3 C] in attention's channel layout, out [B H W][C], bias [nhead][(2 k - 1)^2] fp32.
+    Per sample, head and pixel O = softmax(q K^T / sqrt(d) + bias) V over the k k keys of the pixel's
+    clamped neighbourhood; st.lse receives every row's log-sum-exp.  out must not alias qkv.
+    bf16_products: as attn_forward."""
+    H, W, k = st.geom
+    rows, C3 = qkv.shape
+    C = C3 // 3
+    n = B * nhead * H * W
+    if rows != B * H * W or n > st.lse.shape[0]:
+        raise ValueError("nattn_forward: %d rows at batch %d, state sized for %d" % (rows, B, st.lse.shape[0]))
+    if qkv.data_ptr() == out.data_ptr():
+        raise ValueError("nattn_forward: out must not alias qkv (backward reads qkv again)")
+    if not _native_t(qkv):
+        _, _, v, s, _, _ = _nattn_logits(qkv, bias, B, nhead, st)
+        lse = torch.logsumexp(s, -1, keepdim=True)
+        st.lse[:n].copy_(lse.reshape(-1))
+        p = torch.exp(s - lse)
+        out.copy_(torch.einsum("bhpj,bpjhd->bphd", _bf16_round(p) if bf16_products else p, v).reshape(rows, C))
+        return
+    _flat_bf16(qkv, out, who="nattn_forward")
+    native.check(_k().cxn_nattn_fwd(qkv.data_ptr(), out.data_ptr(), bias.data_ptr(), st.lse.data_ptr(),
+                                    st.lse2.data_ptr(), B, H, W, C, nhead, k, _stream()), "nattn_fwd")
+
+
+def nattn_backward(g, qkv, dqkv, bias, gbias, B, nhead, st: NAttnState, prop_grad: bool, bf16_products=False):
+    """g [B H W][C] = dO.  With P of the last forward, dP = dO V^T, D_i = sum_j P_ij dP_ij (into
+    st.dsum) and dS = P (dP - D) over each pixel's neighbourhood: gbias[h][r] += sum of dS over the
+    batch and the (query, key) pairs at relative index r (always), and with prop_grad dQ = dS K /
+    sqrt(d), dK = dS^T Q / sqrt(d), dV = P^T dO -- a key collects from every query that attends it --
+    into dqkv [B H W][3 C], which may be qkv (dQ then passes through st.dq).  bf16_products: as
+    attn_backward (gbias takes the unrounded dS either way, as in the kernels)."""
+    H, W, k = st.geom
+    rows, C3 = qkv.shape
+    C = C3 // 3
+    n = B * nhead * H * W
+    if not _native_t(g):
+        q, kk, v, s, nbr, rel = _nattn_logits(qkv, bias, B, nhead, st)
+        d = C // nhead
+        sc = 1.0 / d ** 0.5
+        do = (g if g.dtype == torch.float64 else g.float()).view(B, H * W, nhead, d)
+        p = torch.exp(s - st.lse[:n].view(B, nhead, H * W, 1).to(s.dtype))
+        dp = torch.einsum("bphd,bpjhd->bhpj", do, v)
+        dsum = (p * dp).sum(-1, keepdim=True)
+        st.dsum[:n].copy_(dsum.reshape(-1))
+        ds = p * (dp - dsum)
+        gbias.index_add_(1, rel.reshape(-1), ds.sum(0).reshape(nhead, -1).to(gbias.dtype))
+        if not prop_grad:
+            return
+        if bf16_products:
+            p, ds = _bf16_round(p), _bf16_round(ds)
+        dq = torch.einsum("bhpj,bpjhd->bphd", ds, kk) * sc
+        zero = torch.zeros_like(dq)
+        dk = zero.index_add(1, nbr.reshape(-1), (torch.einsum("bhpj,bphd->bpjhd", ds, q) * sc).reshape(B, -1, nhead, d))
+        dv = zero.index_add(1, nbr.reshape(-1), torch.einsum("bhpj,bphd->bpjhd", p, do).reshape(B, -1, nhead, d))
+        dqkv.copy_(torch.stack([dq, dk, dv], 2).reshape(rows, C3))
+        return
+    _flat_bf16(g, qkv, who="nattn_backward")
+    if prop_grad:
+        _flat_bf16(dqkv, who="nattn_backward")
+    stage = st.stage(qkv.device).data_ptr() if prop_grad and dqkv.data_ptr() == qkv.data_ptr() else None
+    native.check(_k().cxn_nattn_bwd(qkv.data_ptr(), g.data_ptr(), bias.data_ptr(), st.lse2.data_ptr(),
+                                    st.dsum.data_ptr(), dqkv.data_ptr() if prop_grad else None, stage,
+                                    gbias.data_ptr(), st.ws.data_ptr(), st.ws.numel(), B, H, W, C, nhead, k,
+                                    _stream()), "nattn_bwd")
 
 
 # ----------------------------------------------------------------------------- kv attention
